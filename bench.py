@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native Groth16 hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--mode weak|strong] [--total-log2n 26] [--proofs P]
+    python bench.py --gpus N --steps K --warmup W [--mode weak|strong] [--total-log2n 26] [--dump-outputs DIR]
+                    [--full [--proofs P] [--no-cpu-baseline]]
 
 Headline (`value`, BASELINE.json configs[1]): BN254 G1 Pippenger MSM, 2^20 points per GPU, uniform random scalars in
 [0, r), bases (i+1)*G -- all resident in HBM before the timed region.  One "step" = one complete MSM (digits -> bucket
 sort -> bucket accumulation -> weighted bucket reduction -> Horner combine -> XYZZ result on the host).  Steps are
 software-pipelined four deep over the context's MSM lanes (stream + workspace each); the timed region still contains
-exactly K complete MSMs, each fully reduced to one point, and the last result is checked (untimed) against the closed
-form  sum_i s_i (i+1) * G.
+exactly K complete MSMs, each fully reduced to one point; with `--full` the last result is checked (untimed) against
+the closed form  sum_i s_i (i+1) * G.
 
 Multi-GPU.  `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process before anything touches the GPU and
@@ -18,7 +19,14 @@ exits with its return code (the driver's own torchrun launch is used as it is). 
   --mode strong BASELINE config 5: ONE MSM of 2^total-log2n points (default 2^26), rank k takes
                 sharding.shard_range(2^26, N, k); same exchange; `scaling` = "strong"
 
-The same JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step and the run's shape).  `--dump-outputs DIR` writes the last timed step's result, the affine point a caller
+receives, as DIR/msm_result_g1_affine.npy; the inputs are the same from run to run.  With `--full` the same JSON line
+also carries
+  cold, driver_warmup_only
+                two fresh child processes before the main run: the first MSMs without prewarm, and W + K steps without prewarm
+  result_checked
+                the last step's result against the closed form  sum_i s_i (i+1) * G  (a mismatch ends the run)
   proof         BASELINE config 3 / 4: full Groth16 proofs of a synthetic Keyless-shape key (nVars 1,343,588, N = 2^21,
                 8.3 M coefficients) on every rank (one prover per GPU, replicas): proofs/s over all ranks, p50 / p99
                 latency through k16_prover_prove_mem, and (world size 1) through the file-based C++ FullProver facade
@@ -27,7 +35,8 @@ The same JSON line also carries
   strong_2p26   BASELINE config 5 (round 6): ONE 2^26-point G1 MSM -- eight shards through k16_msm_sharded_* at N = 1, one shard per
                 rank + libk16.so's k16_rank_comm_* (ONE ncclAllGather) at N > 1 -- closed form checked
                 (both after the timed region; K16_BENCH_NO_CONFIG_LEGS=1 skips them)
-  roofline      for the dominant kernel (bucket accumulation): algorithmic bytes / measured launch time
+  roofline      for the dominant kernel (bucket accumulation): algorithmic bytes / measured launch time; with
+                stage_ms_isolated, host_ms and host_scalars_leg
   cpu_baseline  the CPU oracle (oracle/, a port of the reference algorithm) timed on this host on the same MSM workload
                 and on ONE full proof of the same key, which is also the check of the GPU proof (rank 0, N = 1 only)
 """
@@ -117,6 +126,16 @@ def scalar_times_g(ctx, k16, k):
     d_g.free()
     d_k.free()
     return aff
+
+
+def dump_outputs(out_dir, k16, xyzz):
+    """--dump-outputs: the last timed step's MSM result as the affine point a caller receives (x | y, Montgomery form,
+    little-endian), each coordinate as 16 limbs of 16 bits in float64 (exact), shape (2, 16).  The XYZZ form is not
+    written: it is not unique, and two correct builds may return different XYZZ coordinates for the same point."""
+    _, aff = k16.points_sum(k16.G1, np.frombuffer(xyzz, dtype=np.uint8).reshape(1, 128))
+    limbs = np.frombuffer(aff, dtype="<u2").reshape(2, 16).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result_g1_affine.npy"), limbs)
 
 
 # ---------------------------------------------------------------------------------------------------- CPU baseline
@@ -1019,12 +1038,18 @@ def main():
     ap.add_argument("--log2n", type=int, default=LOG2N)
     ap.add_argument("--mode", choices=("weak", "strong"), default="weak")
     ap.add_argument("--total-log2n", type=int, default=26, help="strong mode: the whole MSM has 2^this points")
-    ap.add_argument("--proofs", type=int, default=20, help="full Keyless-shape proofs per rank in the proof leg (0: skip it)")
-    ap.add_argument("--proof-scale", type=float, default=1.0, help="shrink the synthetic circuit (1.0 = Keyless shape)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures and checks: cold and warm-up-only probes, closed-form check, roofline, "
+                         "host-scalars leg, proofs, BASELINE configs 4 / 5, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's result as DIR/<name>.npy")
+    ap.add_argument("--proofs", type=int, default=20, help="--full: Keyless-shape proofs per rank in the proof leg (0: skip it)")
+    ap.add_argument("--proof-scale", type=float, default=1.0, help="--full: shrink the synthetic circuit (1.0 = Keyless shape)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cold-probe", action="store_true", help=argparse.SUPPRESS)   # child of the main run, see cold_probe()
     ap.add_argument("--warm-only-probe", action="store_true", help=argparse.SUPPRESS)   # child: W warm-up + K steps, no prewarm
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cold_probe:
         return cold_probe_child(args)
     if args.warm_only_probe:
@@ -1040,7 +1065,7 @@ def main():
         sys.exit("bench.py: --gpus %d but WORLD_SIZE=%d: launch one rank per GPU" % (n_gpus, world))
 
     # the cold figures come from a child process that runs (and ends) before this one touches the GPU
-    cold = cold_probe(args) if (world == 1 and args.mode == "weak" and not os.environ.get("K16_BENCH_NO_COLD")) else None
+    cold = cold_probe(args) if (args.full and world == 1 and args.mode == "weak" and not os.environ.get("K16_BENCH_NO_COLD")) else None
     warm_only = cold_probe(args, "--warm-only-probe") if cold is not None else None
 
     # ROCm multiplexes a process's HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  Four MSM lanes fill
@@ -1272,8 +1297,9 @@ def main():
         got = [c.stats_get(name) for c in stat_ctxs]
         return sum(g[0] for g in got), sum(g[1] for g in got)
 
-    stats_enable(2)   # HIP events around the dominant kernel only (2 per MSM): the timed region stays lean
-    stats_reset()
+    if args.full:
+        stats_enable(2)   # HIP events around the dominant kernel only (2 per MSM): the timed region stays lean
+        stats_reset()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -1289,23 +1315,26 @@ def main():
               file=sys.stderr, flush=True)
         print("[bench trace] enqueue ms (all steps incl. warm-up): " + " ".join("%.2f" % v for v in enq_times),
               file=sys.stderr, flush=True)
-    launches, acc_ms = stats_get("msm_accumulate")
-    # host side of one step (C entry points only): launches, waiting for the GPU, conversion + Horner
-    host_ms = {k: stats_get(k)[1] / max(stats_get(k)[0], 1)
-               for k in ("host_enqueue", "host_finish_wait", "host_finish_combine", "host_enqueue_max")}
-    # the same kernel without a neighbour on the GPU (one MSM at a time), for reference next to the live figure; this
-    # untimed pass also times the other stages
-    stats_enable(1)
-    stats_reset()
-    saved_depth = depth_cell[0]
-    depth_cell[0] = 1
-    lane[0] = 0
-    run(1 if chunked else 3)
-    depth_cell[0] = saved_depth
-    iso_launches, iso_ms = stats_get("msm_accumulate")
-    stage_ms = {k: stats_get(k)[1] / max(stats_get(k)[0], 1)
-                for k in ("msm_sort", "msm_accumulate", "msm_fold", "msm_reduce")}
-    stats_enable(0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, k16, result)
+    if args.full:
+        launches, acc_ms = stats_get("msm_accumulate")
+        # host side of one step (C entry points only): launches, waiting for the GPU, conversion + Horner
+        host_ms = {k: stats_get(k)[1] / max(stats_get(k)[0], 1)
+                   for k in ("host_enqueue", "host_finish_wait", "host_finish_combine", "host_enqueue_max")}
+        # the same kernel without a neighbour on the GPU (one MSM at a time), for reference next to the live figure; this
+        # untimed pass also times the other stages
+        stats_enable(1)
+        stats_reset()
+        saved_depth = depth_cell[0]
+        depth_cell[0] = 1
+        lane[0] = 0
+        run(1 if chunked else 3)
+        depth_cell[0] = saved_depth
+        iso_launches, iso_ms = stats_get("msm_accumulate")
+        stage_ms = {k: stats_get(k)[1] / max(stats_get(k)[0], 1)
+                    for k in ("msm_sort", "msm_accumulate", "msm_fold", "msm_reduce")}
+        stats_enable(0)
 
     ranks_seen = 1
     if dist is not None:
@@ -1315,25 +1344,26 @@ def main():
         ranks_seen = dist.get_world_size()
 
     # untimed: the last step's (folded) result against the closed form  (sum over all shards of s_i * (start + i + 1)) * G
-    k_mine = weighted_sum_mod_r(scalars, start)
-    if dist is not None:
-        ks = [None] * ranks_seen
-        dist.all_gather_object(ks, k_mine)
-        k_all = sum(ks) % R_MOD
-    else:
-        k_all = k_mine
     result_checked = None
-    if rank == 0:
-        _, got_aff = k16.points_sum(k16.G1, np.frombuffer(result, dtype=np.uint8).reshape(1, 128))
-        result_checked = bool(got_aff == scalar_times_g(ctx, k16, k_all))
-        if not result_checked and not os.environ.get("K16_BENCH_NOCHECK"):   # (probe runs produce wrong results on purpose)
-            raise SystemExit("bench.py: MSM result differs from the closed form sum s_i (i+1) * G")
+    if args.full:
+        k_mine = weighted_sum_mod_r(scalars, start)
+        if dist is not None:
+            ks = [None] * ranks_seen
+            dist.all_gather_object(ks, k_mine)
+            k_all = sum(ks) % R_MOD
+        else:
+            k_all = k_mine
+        if rank == 0:
+            _, got_aff = k16.points_sum(k16.G1, np.frombuffer(result, dtype=np.uint8).reshape(1, 128))
+            result_checked = bool(got_aff == scalar_times_g(ctx, k16, k_all))
+            if not result_checked and not os.environ.get("K16_BENCH_NOCHECK"):   # (probe runs produce wrong results on purpose)
+                raise SystemExit("bench.py: MSM result differs from the closed form sum s_i (i+1) * G")
 
     # ---- secondary figure: the shape of Curve::multiMulByScalar's contract (curve.hpp:209-215) -- scalars arrive in HOST memory
     # (page-locked) every call, the result goes back to the host; bases stay resident (a prover's tables are static).  One MSM
     # at a time: upload, sort, accumulate, reduce, combine, no overlap between calls.  PCIe-inclusive, never `value`.
     host_leg = None
-    if rank == 0 and not strong and not chunked and not os.environ.get("K16_BENCH_NO_HOST_LEG"):
+    if args.full and rank == 0 and not strong and not chunked and not os.environ.get("K16_BENCH_NO_HOST_LEG"):
         try:
             pinned = torch.from_numpy(scalars).pin_memory()
             hp = pinned.numpy()
@@ -1365,7 +1395,7 @@ def main():
     d_scalars.free()
     proof = None
     ctx.set_option(k16.OPT_PIPELINED_MSM, 0)   # the prover wants the latency-tuned defaults (include/k16.h)
-    if args.proofs > 0:
+    if args.full and args.proofs > 0:
         # the prover gets a context of its own, as in a service: the MSM bench's context has four lane streams, and a stream
         # the prover never uses still costs a proof ~0.4 ms (p50 7.9 vs 7.5 ms measured; ROCm multiplexes a process's streams
         # onto its hardware queues)
@@ -1375,11 +1405,11 @@ def main():
         proof = proof_leg(ctx, k16, torch, dist, rank, world, args.proofs,
                           check_with_oracle=(world == 1 and not args.no_cpu_baseline), scale=args.proof_scale)
 
-    # ---- BASELINE configs 4 and 5 as secondary legs of the SAME line, after the timed region (round 6): ON by default so that
-    # the driver's one command records them at every N; K16_BENCH_NO_CONFIG_LEGS=1 (or _NO_WAVE / _NO_2P26) skips them for quick
+    # ---- BASELINE configs 4 and 5 as secondary legs of the SAME line, after the timed region (round 6): part of every --full
+    # run, at every N; K16_BENCH_NO_CONFIG_LEGS=1 (or _NO_WAVE / _NO_2P26) skips them for quick
     # runs, K16_BENCH_2P26_LOG2N / K16_BENCH_WAVE_SCALE shrink them for the test suite
     legs = {}
-    no_legs = bool(os.environ.get("K16_BENCH_NO_CONFIG_LEGS"))
+    no_legs = not args.full or bool(os.environ.get("K16_BENCH_NO_CONFIG_LEGS"))
     if not no_legs and not os.environ.get("K16_BENCH_NO_WAVE"):
         try:
             legs["config4_wave"] = config4_wave_leg(k16, torch, dist, rank, world, dev, int(os.environ.get("K16_BENCH_WAVE", "64")),
@@ -1406,29 +1436,6 @@ def main():
         if not strong:
             total_points *= world
         value = total_points / elapsed
-        kern_s = (acc_ms / max(launches, 1)) * 1e-3
-        # rows one launch of the dominant kernel covers: the whole MSM up to 2^24 rows, a 2^24-row chunk above, one PIECE of one
-        # shard (k16_msm_sharded_*: 2^22 rows of host scalars per device pass) in the one-process sharded run
-        pts_per_launch = min(n, 1 << 24) if shards_obj is None else min((n + len(shard_devices) - 1) // len(shard_devices), 1 << 22)
-        achieved = (pts_per_launch * ALGO_BYTES_PER_POINT) / kern_s / 1e9 if kern_s > 0 else 0.0
-        traffic, traffic_src = None, None
-        tp = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tp) and not strong and args.log2n == 20:
-            try:
-                tj = json.load(open(tp))
-                # the counters were collected for ONE build of the kernel: the file carries a digest of the sources that
-                # make k_accumulate<Eng9>; a tree whose kernel sources differ reports no traffic figure instead of a stale one
-                if tj.get("kernel_sources_sha16") == kernel_sources_sha16():
-                    traffic = tj.get("msm_accumulate_hbm_bytes_per_launch")
-                    traffic_src = "replayed from profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this " \
-                                  "command at commit %s, same kernel sources as this tree: digest %s; not measured in this run)" \
-                                  % (tj.get("commit"), tj.get("kernel_sources_sha16"))
-                else:
-                    traffic_src = "profiles/pmc_traffic.json was collected for other kernel sources (digest %s, this tree %s): " \
-                                  "no figure" % (tj.get("kernel_sources_sha16"), kernel_sources_sha16())
-            except Exception:
-                traffic = None
-        iso = iso_ms / max(iso_launches, 1)
         out = {
             "metric": "BN254 G1 MSM points/s @2^%d (Groth16 prover hot path)" % (args.total_log2n if strong else args.log2n),
             "value": value,
@@ -1438,9 +1445,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "prewarm_steps": prewarm,
-            "value_driver_warmup_only": (warm_only or {}).get("value"),
-            "driver_warmup_only": warm_only,
-            "cold": cold,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
@@ -1448,7 +1452,6 @@ def main():
             "dtype": "u64 column accumulators over 9 x 29-bit limbs (256-bit Montgomery integers, v_mad_u64_u32)",
             "data": "synthetic: bases (i+1)*G generated on device, scalars uniform in [0,%s) (numpy seed 0xD1B5+rank)"
                     % ("2^253" if strong else "r"),
-            "result_checked": result_checked,
             "config": {
                 "workload": ("BN254 G1 Pippenger MSM, ONE MSM of 2^%d points sharded over the ranks, result XYZZ on host"
                              % args.total_log2n) if strong else
@@ -1470,55 +1473,85 @@ def main():
                              % (len(shard_devices), shard_devices)),
                 "exchange_note": c_exchange_note,
             },
-            "roofline": {
-                "kernel": "k_accumulate<Eng9> (bucket accumulation, XYZZ mixed adds)",
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "kernel_ms": kern_s * 1e3,
-                "kernel_ms_isolated": iso,
-                "frac_isolated": (pts_per_launch * ALGO_BYTES_PER_POINT) / (iso * 1e-3) / 1e9 / HBM_PEAK_GBS if iso > 0 else None,
-                # the same launch priced in the unit that actually bounds it: 254-bit modular multiplications
-                "alu": {
-                    "unit": "G modmul/s",
-                    "achieved": pts_per_launch * 16 * MODMUL_PER_PAIR / (iso * 1e-3) / 1e9 if iso > 0 else None,
-                    "peak": MODMUL_PEAK_G,
-                    "frac": pts_per_launch * 16 * MODMUL_PER_PAIR / (iso * 1e-3) / 1e9 / MODMUL_PEAK_G if iso > 0 else None,
-                    "frac_step": pts_per_launch * 16 * MODMUL_PER_PAIR / (elapsed / args.steps) / 1e9 / MODMUL_PEAK_G / (world if not strong else 1),
-                    # ... and against the hardware's multiply-add issue rate (31.9 T v_mad_u64_u32 lane-ops/s / 162 per product)
-                    "peak_hw": MODMUL_PEAK_HW_G,
-                    "frac_hw": pts_per_launch * 16 * MODMUL_PER_PAIR / (iso * 1e-3) / 1e9 / MODMUL_PEAK_HW_G if iso > 0 else None,
-                    "frac_step_hw": pts_per_launch * 16 * MODMUL_PER_PAIR / (elapsed / args.steps) / 1e9 / MODMUL_PEAK_HW_G / (world if not strong else 1),
-                    "frac_step_basis": "the same algorithmic multiplications over the whole STEP (ms_per_step: sort, accumulation, "
-                                       "fold, weighted sum, host combine of one MSM per lane, four lanes pipelined), per GPU",
-                    "basis": "algorithmic 10 modmul x n x 16 windows per launch / kernel_ms_isolated; peak = measured "
-                             "v_mad_u64_u32-bound multiply rate of the radix-2^29 field (no MFMA path exists for 254-bit integers)",
-                },
-                "note": "kernel_ms is the live average inside the timed region (HIP events on the kernel's stream; up to "
-                        "four MSMs share the GPU, and the other lanes' sort / reduction kernels run beside it at a higher "
-                        "wave priority, so their instructions are issued inside this interval: +0.3 ms over isolated, "
-                        "+2 % points/s over not prioritising them); kernel_ms_isolated is the same kernel with one MSM at a "
-                        "time. Integer-multiply-issue bound in practice; see DESIGN.md (modmul-rate view)",
-            },
-            "stage_ms_isolated": stage_ms,
-            "host_ms": host_ms,
-            "host_scalars_leg": host_leg,
-            "proof": proof,
         }
-        out.update(legs)
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                n_cpu = 1 << min(args.log2n, 20)
-                out["cpu_baseline"] = cpu_baseline(n_cpu, uniform_scalars(n_cpu, seed=0xD1B5) if strong else scalars)
-                if proof and proof.get("cpu_oracle"):
-                    out["cpu_baseline"]["proof"] = proof.pop("cpu_oracle")
-            except Exception as e:  # the baseline is a report, never the measured path
-                out["cpu_baseline"] = {"value": None, "unit": "points/s", "cores": 0, "kind": "port",
-                                       "sample": "failed: %r" % (e,)}
+        if args.full:
+            kern_s = (acc_ms / max(launches, 1)) * 1e-3
+            # rows one launch of the dominant kernel covers: the whole MSM up to 2^24 rows, a 2^24-row chunk above, one PIECE of one
+            # shard (k16_msm_sharded_*: 2^22 rows of host scalars per device pass) in the one-process sharded run
+            pts_per_launch = min(n, 1 << 24) if shards_obj is None else min((n + len(shard_devices) - 1) // len(shard_devices), 1 << 22)
+            achieved = (pts_per_launch * ALGO_BYTES_PER_POINT) / kern_s / 1e9 if kern_s > 0 else 0.0
+            traffic, traffic_src = None, None
+            tp = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tp) and not strong and args.log2n == 20:
+                try:
+                    tj = json.load(open(tp))
+                    # the counters were collected for ONE build of the kernel: the file carries a digest of the sources that
+                    # make k_accumulate<Eng9>; a tree whose kernel sources differ reports no traffic figure instead of a stale one
+                    if tj.get("kernel_sources_sha16") == kernel_sources_sha16():
+                        traffic = tj.get("msm_accumulate_hbm_bytes_per_launch")
+                        traffic_src = "replayed from profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this " \
+                                      "command at commit %s, same kernel sources as this tree: digest %s; not measured in this run)" \
+                                      % (tj.get("commit"), tj.get("kernel_sources_sha16"))
+                    else:
+                        traffic_src = "profiles/pmc_traffic.json was collected for other kernel sources (digest %s, this tree %s): " \
+                                      "no figure" % (tj.get("kernel_sources_sha16"), kernel_sources_sha16())
+                except Exception:
+                    traffic = None
+            iso = iso_ms / max(iso_launches, 1)
+            out.update({
+                "value_driver_warmup_only": (warm_only or {}).get("value"),
+                "driver_warmup_only": warm_only,
+                "cold": cold,
+                "result_checked": result_checked,
+                "roofline": {
+                    "kernel": "k_accumulate<Eng9> (bucket accumulation, XYZZ mixed adds)",
+                    "bound": "hbm",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic,
+                    "traffic_source": traffic_src,
+                    "kernel_ms": kern_s * 1e3,
+                    "kernel_ms_isolated": iso,
+                    "frac_isolated": (pts_per_launch * ALGO_BYTES_PER_POINT) / (iso * 1e-3) / 1e9 / HBM_PEAK_GBS if iso > 0 else None,
+                    # the same launch priced in the unit that actually bounds it: 254-bit modular multiplications
+                    "alu": {
+                        "unit": "G modmul/s",
+                        "achieved": pts_per_launch * 16 * MODMUL_PER_PAIR / (iso * 1e-3) / 1e9 if iso > 0 else None,
+                        "peak": MODMUL_PEAK_G,
+                        "frac": pts_per_launch * 16 * MODMUL_PER_PAIR / (iso * 1e-3) / 1e9 / MODMUL_PEAK_G if iso > 0 else None,
+                        "frac_step": pts_per_launch * 16 * MODMUL_PER_PAIR / (elapsed / args.steps) / 1e9 / MODMUL_PEAK_G / (world if not strong else 1),
+                        # ... and against the hardware's multiply-add issue rate (31.9 T v_mad_u64_u32 lane-ops/s / 162 per product)
+                        "peak_hw": MODMUL_PEAK_HW_G,
+                        "frac_hw": pts_per_launch * 16 * MODMUL_PER_PAIR / (iso * 1e-3) / 1e9 / MODMUL_PEAK_HW_G if iso > 0 else None,
+                        "frac_step_hw": pts_per_launch * 16 * MODMUL_PER_PAIR / (elapsed / args.steps) / 1e9 / MODMUL_PEAK_HW_G / (world if not strong else 1),
+                        "frac_step_basis": "the same algorithmic multiplications over the whole STEP (ms_per_step: sort, accumulation, "
+                                           "fold, weighted sum, host combine of one MSM per lane, four lanes pipelined), per GPU",
+                        "basis": "algorithmic 10 modmul x n x 16 windows per launch / kernel_ms_isolated; peak = measured "
+                                 "v_mad_u64_u32-bound multiply rate of the radix-2^29 field (no MFMA path exists for 254-bit integers)",
+                    },
+                    "note": "kernel_ms is the live average inside the timed region (HIP events on the kernel's stream; up to "
+                            "four MSMs share the GPU, and the other lanes' sort / reduction kernels run beside it at a higher "
+                            "wave priority, so their instructions are issued inside this interval: +0.3 ms over isolated, "
+                            "+2 % points/s over not prioritising them); kernel_ms_isolated is the same kernel with one MSM at a "
+                            "time. Integer-multiply-issue bound in practice; see DESIGN.md (modmul-rate view)",
+                },
+                "stage_ms_isolated": stage_ms,
+                "host_ms": host_ms,
+                "host_scalars_leg": host_leg,
+                "proof": proof,
+            })
+            out.update(legs)
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    n_cpu = 1 << min(args.log2n, 20)
+                    out["cpu_baseline"] = cpu_baseline(n_cpu, uniform_scalars(n_cpu, seed=0xD1B5) if strong else scalars)
+                    if proof and proof.get("cpu_oracle"):
+                        out["cpu_baseline"]["proof"] = proof.pop("cpu_oracle")
+                except Exception as e:  # the baseline is a report, never the measured path
+                    out["cpu_baseline"] = {"value": None, "unit": "points/s", "cores": 0, "kind": "port",
+                                           "sample": "failed: %r" % (e,)}
         print(json.dumps(out), flush=True)
 
     if dist is not None:

@@ -20,7 +20,7 @@ def _threads_of_process():
     return -1
 
 
-def test_eight_provers_share_one_host_pool_and_keep_the_throughput():
+def test_eight_provers_share_one_host_pool_and_keep_the_throughput(tmp_path):
     """Eight contexts with a prover each on ONE GPU (K16_DEVICES=0,0,0,0,0,0,0,0 in FullProver terms), a circuit large
     enough for the compact witness upload (the pool's main user): the pool's size does not depend on the number of
     provers and stays within the CPUs the process may use; proofs are the same bytes from every prover; eight provers
@@ -32,7 +32,7 @@ def test_eight_provers_share_one_host_pool_and_keep_the_throughput():
     ctx0 = k16.Context(0)
     n_vars, N, n_coefs = 335897, 1 << 19, 2075000          # the Keyless shape at scale 1/4
     zk = bench.synth_zkey_bytes(ctx0, k16, n_vars, 1, N, n_coefs)
-    zpath = "/tmp/k16_threads_test.zkey"
+    zpath = str(tmp_path / "threads_test.zkey")
     with open(zpath, "wb") as f:
         f.write(zk)
     del zk

@@ -16,16 +16,38 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(args, env_extra, timeout=900):
+def _bench(args, env_extra, timeout=900, full=True):
     env = dict(os.environ, **env_extra)
     env.setdefault("K16_BENCH_NO_CONFIG_LEGS", "1")     # (the config 4 / 5 legs have tests of their own below)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
-                         timeout=timeout, env=env, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + (["--full"] if full else []) + args,
+                         capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     return json.loads(line)
+
+
+def test_bench_plain_run_reports_the_headline_and_dumps_the_checked_result(tmp_path):
+    """A plain run (no --full): the headline line without the secondary figures, and --dump-outputs writes the last timed
+    step's affine result, which equals the closed form (sum_i s_i (i+1)) G of bench.py's seeded inputs."""
+    import numpy as np
+    import bench
+    import k16
+    log2n = 14
+    d = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--log2n", str(log2n), "--dump-outputs", str(tmp_path)],
+               {"K16_BENCH_PREWARM": "1"}, full=False)
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "points/s" and "2^%d" % log2n in d["metric"] and d["dtype"]
+    assert not {"cold", "result_checked", "roofline", "host_scalars_leg", "proof", "cpu_baseline"} & set(d), sorted(d)
+    limbs = np.load(tmp_path / "msm_result_g1_affine.npy")
+    assert limbs.dtype == np.float64 and limbs.shape == (2, 16)
+    ctx = k16.Context(0)
+    try:
+        want = bench.scalar_times_g(ctx, k16, bench.weighted_sum_mod_r(bench.uniform_scalars(1 << log2n, 0xD1B5), 0))
+    finally:
+        ctx.close()
+    assert limbs.astype("<u2").tobytes() == want
 
 
 @pytest.mark.parametrize("mode_args, scaling", [(["--log2n", "16"], "weak"),

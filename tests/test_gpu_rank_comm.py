@@ -122,7 +122,7 @@ def test_bench_strong_mode_two_ranks_through_the_c_exchange_over_the_double(fake
                K16_BENCH_NO_CONFIG_LEGS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mode",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--mode",
                           "strong", "--total-log2n", "20", "--proofs", "0", "--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
@@ -141,7 +141,7 @@ def test_bench_weak_mode_two_ranks_overlap_their_exchanges_through_the_c_leg(fak
                FAKE_RCCL_ASYNC=async_mode)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "K16_BENCH_EXCHANGE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--log2n", "16",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "2", "--log2n", "16",
                           "--proofs", "0", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -159,7 +159,7 @@ def test_bench_eight_ranks_rehearsal_over_the_double(fake):
                K16_BENCH_2P26_LOG2N="22", K16_BENCH_PROVERS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "K16_BENCH_EXCHANGE", "K16_BENCH_NO_CONFIG_LEGS"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1", "--log2n", "16",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "4", "--warmup", "1", "--log2n", "16",
                           "--proofs", "2", "--proof-scale", "0.05", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200,
                          env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]

@@ -4,7 +4,7 @@
 out=$1; shift
 mkdir -p "$out"
 reps=${REPS:-2}
-args=${AB_ARGS:---steps 20 --warmup 5 --proofs 0 --no-cpu-baseline}
+args=${AB_ARGS:---full --steps 20 --warmup 5 --proofs 0 --no-cpu-baseline}
 for r in $(seq 1 $reps); do
   i=0
   for cfg in "$@"; do

@@ -1,5 +1,5 @@
 """Kernel timeline of the FIRST steps of the pipelined MSM bench's timed region (pipeline fill), from a rocprofv3 kernel trace:
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 20 --warmup 5 --proofs 0 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --steps 20 --warmup 5 --proofs 0 --no-cpu-baseline
     python3 tools/lab/msm_fill_timeline.py DIR [steps=20] [show_ms=6]
 The timed region's accumulations are the last `steps` k_accumulate<Eng9> launches (bench.py's isolated pass of 3 MSMs follows: skipped)."""
 import csv, glob, os, sys

@@ -1,5 +1,5 @@
 """Gaps between consecutive bucket accumulations of the pipelined MSM bench, and what runs inside them (dev aid):
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 20 --warmup 5 --proofs 0 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --steps 20 --warmup 5 --proofs 0 --no-cpu-baseline
     python3 tools/lab/msm_pipeline_gaps.py DIR"""
 import csv, glob, os, sys
 d = sys.argv[1]

@@ -2,7 +2,7 @@
 # samples rocm-smi power / clocks while a bench configuration runs:  tools/lab/power_probe.sh "ENV=.. ENV=.." [steps]
 cfg="$1"; steps=${2:-4000}
 if [ "$cfg" = "-" ]; then cfg=""; fi
-env $cfg K16_BENCH_NOCHECK=1 python3 bench.py --steps $steps --warmup 5 --proofs 0 --no-cpu-baseline > /tmp/pp.json 2>/tmp/pp.err &
+env $cfg K16_BENCH_NOCHECK=1 python3 bench.py --full --steps $steps --warmup 5 --proofs 0 --no-cpu-baseline > /tmp/pp.json 2>/tmp/pp.err &
 pid=$!
 sleep 16
 for i in 1 2 3 4 5 6 7 8; do

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for node in sorted(glob.glob("/sys/devices/system/node/node*")):
     cl = open(node + "/cpulist").read().strip()
     env = dict(os.environ, K16_BENCH_CPUS=cl)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"], capture_output=True, text=True, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])
         print(os.path.basename(node), cl[:30], "->", round(d["value"] / 1e6, 1), "M/s", d["ms_per_step"], d["host_ms"])
