@@ -398,8 +398,8 @@ int  k16_prover_warmup_status(const k16_prover* p);
  * otherwise be interchangeable) or does not lie on the curve (A, C) / the twist (B) is REJECTED (flag 0), as ark's
  * deserialisation refuses it before verify_proof runs.  Membership of B in the r-torsion subgroup is NOT tested (the
  * service verifies its own prover's output; aptos-types validates foreign points when it deserialises them): a caller that
- * verifies proofs from elsewhere must do that first.  Points with a zero coordinate pair count as the point at infinity
- * (the pair then contributes 1, as ark-ec's multi_miller_loop skips it). */
+ * verifies proofs from elsewhere calls k16_verify_batch_checked below, which adds that test.  Points with a zero
+ * coordinate pair count as the point at infinity (the pair then contributes 1, as ark-ec's multi_miller_loop skips it). */
 typedef struct k16_vk k16_vk;
 int  k16_vk_create(k16_ctx* ctx, const void* alpha1_g1, const void* beta2_g2, const void* gamma2_g2, const void* delta2_g2,
                    const void* ic_g1, uint32_t n_ic, k16_vk** out);
@@ -414,6 +414,32 @@ int  k16_verify_coop_gt(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, co
 /* parity tests: out[i] = e(P_i, Q_i) exactly as ark-ec's Bn::pairing gives it, 12 x 32 B per value (Fq12 = Fq6[w]/(w^2 - v),
  * Fq6 = Fq2[v]/(v^3 - 9 - u): c0.c0.a, c0.c0.b, c0.c1.a, ...), Montgomery form */
 int  k16_pairing_vec(k16_ctx* ctx, const void* h_g1, const void* h_g2, uint64_t n, void* h_out_gt);
+
+/* ---- point validation on the GPU: what ark-serialize's validated deserialisation checks ----
+ * Status of a point: its coordinates are canonical (< p), checked first; then it lies on the curve (G1) or the twist (G2);
+ * then, for G2 only, it lies in the order-r subgroup (the twist's cofactor is 2p - r = 10069 x a 241-bit prime; G1's is 1).
+ * The G2 test is the endomorphism test of eprint 2022/348 section 5.1, one lane pair per point (csrc/bn254_points.h). */
+enum { K16_PT_OK = 0, K16_PT_NONCANONICAL = 1, K16_PT_OFF_CURVE = 2, K16_PT_NOT_IN_SUBGROUP = 3 };
+enum { K16_VERIFY_PAIRING_MISMATCH = 4 };
+/* status per point, affine Montgomery LE as everywhere (G1 64 B, G2 128 B); all-zero = infinity = K16_PT_OK.  group is
+ * K16_G1 or K16_G2; the points stream through bounded device buffers, so n is not limited by device memory. */
+int  k16_points_check(k16_ctx* ctx, int group, const void* h_points, uint64_t n, uint8_t* h_status);
+/* k16_verify_batch plus ark's validated deserialisation: out_ok[i] == (k16_verify_batch's flag && B_i in G2).
+ * out_reason (may be NULL): 0 accepted, 1..3 the first failing point's status (A, then B, then C),
+ * 4 = K16_VERIFY_PAIRING_MISMATCH.  The subgroup test of the batch is one launch on a stream of the key's own, running
+ * beside the pairing (the wave-cooperative path for small batches as well as the general one). */
+int  k16_verify_batch_checked(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                              uint8_t* h_out_ok, uint8_t* h_out_reason);
+/* every point of a Groth16 zkey, in the sections that are present: 2 (alpha1, beta1, beta2, gamma2, delta1, delta2 =
+ * indices 0..5), 3 (IC; the prover does not need it and synthetic keys omit it), 5 (A), 6 (B1), 7 (B2), 8 (C), 9 (H).
+ * K16_OK with *n_bad = 0 when all pass; otherwise the first failure in (section, index) order and the number of failing
+ * points.  Container / curve errors as k16_prover_create_mem (K16_ERR_FORMAT, K16_ERR_CURVE).  The key streams through
+ * bounded device buffers (two 32 MB chunks): it is never held on the device whole.  Not run by k16_prover_create: the
+ * caller decides when to pay for it. */
+int  k16_zkey_check(k16_ctx* ctx, const void* zkey, size_t size, uint32_t* bad_section, uint64_t* bad_index,
+                    uint8_t* bad_status, uint64_t* n_bad);
+int  k16_zkey_check_file(k16_ctx* ctx, const char* zkey_path, uint32_t* bad_section, uint64_t* bad_index,
+                         uint8_t* bad_status, uint64_t* n_bad);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 #include "ctx.h"
+#include "points_check.h"
 #include "bn254_fq9.h"
 #include "spmv_plan.h"
 
@@ -611,13 +612,17 @@ static void prover_free(k16_prover* p)
 
 static int prover_finish_create(k16_prover* p, k16_prover** out);
 
-extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_t zkey_size, k16_prover** out)
+// The container, protocol, curve and size checks of a Groth16 zkey (fullprover.cpp:150-158, zkey_utils.hpp:54-84): what
+// k16_prover_create_mem and k16_zkey_check both require of a key.  On success hd->pts points at alpha1 in section 2.
+struct ZkeyHeader {
+    uint32_t       n_vars = 0, n_public = 0, domain_size = 0;
+    uint64_t       n_coefs = 0;
+    const uint8_t* pts     = nullptr; // alpha1 (G1) | beta1 (G1) | beta2 (G2) | gamma2 (G2) | delta1 (G1) | delta2 (G2)
+};
+static int zkey_header(k16_ctx* ctx, const uint8_t* base, size_t size, BinView* bv_out, ZkeyHeader* hd)
 {
-    return k16_guard(ctx, [&]() -> int {
-    if (!ctx || !zkey_bytes || !out) return K16_ERR_ARG;
-    *out = nullptr;
-    BinView bv;
-    int     rc = parse_binfile((const uint8_t*)zkey_bytes, zkey_size, "zkey", 1, &bv); // fullprover.cpp:150
+    BinView& bv = *bv_out;
+    int      rc = parse_binfile(base, size, "zkey", 1, &bv); // fullprover.cpp:150
     if (rc) {
         ctx->err = "zkey: not an iden3 zkey container (type/version/sections)";
         return rc;
@@ -653,6 +658,36 @@ extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_
         return K16_ERR_CURVE;
     }
     h += 4 + n8q + 4 + n8r;
+    memcpy(&hd->n_vars, h, 4);
+    memcpy(&hd->n_public, h + 4, 4);
+    memcpy(&hd->domain_size, h + 8, 4);
+    hd->pts     = h + 12;
+    hd->n_coefs = bv.sec[4].size / 44; // zkey_utils.hpp:84 (integer division absorbs the 4-byte count)
+    const uint32_t N = hd->domain_size;
+    if (N == 0 || (N & (N - 1)) || hd->n_vars == 0 || (uint64_t)hd->n_public >= hd->n_vars) { // (64-bit: nPublic = 2^32 - 1 must not wrap)
+        ctx->err = "zkey: bad header sizes";
+        return K16_ERR_FORMAT;
+    }
+    if (bv.sec[5].size < (uint64_t)hd->n_vars * 64 || bv.sec[6].size < (uint64_t)hd->n_vars * 64 ||
+        bv.sec[7].size < (uint64_t)hd->n_vars * 128 ||
+        bv.sec[8].size < (uint64_t)(hd->n_vars - hd->n_public - 1) * 64 || bv.sec[9].size < (uint64_t)N * 64 ||
+        bv.sec[4].size < 4 + hd->n_coefs * 44) {
+        ctx->err = "zkey: section shorter than the header implies";
+        return K16_ERR_FORMAT;
+    }
+    return K16_OK;
+}
+
+extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_t zkey_size, k16_prover** out)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !zkey_bytes || !out) return K16_ERR_ARG;
+    *out = nullptr;
+    BinView    bv;
+    ZkeyHeader zh;
+    int        rc = zkey_header(ctx, (const uint8_t*)zkey_bytes, zkey_size, &bv, &zh);
+    if (rc) return rc;
+    const uint8_t* h = zh.pts;
     k16_prover* p = new k16_prover();
     p->ctx        = ctx;
     // the std containers below (SpMV plan, staging vectors) may throw: the half-built prover then goes with the unwinding
@@ -665,10 +700,9 @@ extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_
             if (std::uncaught_exceptions() > base) prover_free(p);
         }
     } free_on_unwind{p};
-    memcpy(&p->n_vars, h, 4);
-    memcpy(&p->n_public, h + 4, 4);
-    memcpy(&p->domain_size, h + 8, 4);
-    h += 12;
+    p->n_vars      = zh.n_vars;
+    p->n_public    = zh.n_public;
+    p->domain_size = zh.domain_size;
     memcpy(&p->alpha1, h, 64);
     h += 64;
     memcpy(&p->beta1, h, 64);
@@ -678,22 +712,9 @@ extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_
     memcpy(&p->delta1, h, 64);
     h += 64;
     memcpy(&p->delta2, h, 128);
-    p->n_coefs = bv.sec[4].size / 44; // zkey_utils.hpp:84 (integer division absorbs the 4-byte count)
+    p->n_coefs = zh.n_coefs;
     const uint32_t N = p->domain_size;
-    if (N == 0 || (N & (N - 1)) || p->n_vars == 0 || p->n_public + 1 > p->n_vars) {
-        ctx->err = "zkey: bad header sizes";
-        delete p;
-        return K16_ERR_FORMAT;
-    }
     while ((1u << p->logN) < N) p->logN++;
-    if (bv.sec[5].size < (uint64_t)p->n_vars * 64 || bv.sec[6].size < (uint64_t)p->n_vars * 64 ||
-        bv.sec[7].size < (uint64_t)p->n_vars * 128 ||
-        bv.sec[8].size < (uint64_t)(p->n_vars - p->n_public - 1) * 64 || bv.sec[9].size < (uint64_t)N * 64 ||
-        bv.sec[4].size < 4 + p->n_coefs * 44) {
-        ctx->err = "zkey: section shorter than the header implies";
-        delete p;
-        return K16_ERR_FORMAT;
-    }
 
     // regroup the coefficients into rows (spmv_plan.h): length-sorted 64-row slices + long rows
     const uint8_t* cf = bv.sec[4].p + 4;
@@ -996,6 +1017,75 @@ extern "C" int k16_prover_create(k16_ctx* ctx, const char* zkey_path, k16_prover
         return rc;
     }
     return k16_prover_create_mem(ctx, mf.base, mf.size, out);
+    });
+}
+
+// ---------------------------------------------------------------- k16_zkey_check: every point of a key, on the GPU
+// The prover trusts its key; a caller that wants to know whether a downloaded key is intact runs this once (a corrupted
+// point makes every proof invalid).  The header checks are k16_prover_create_mem's; the points stream section by section
+// through the bounded buffers of points_check.hip.  Section 2's points are numbered 0 alpha1, 1 beta1, 2 beta2, 3 gamma2,
+// 4 delta1, 5 delta2.
+static int zkey_check_mem(k16_ctx* ctx, const uint8_t* base, size_t size, uint32_t* bad_section, uint64_t* bad_index,
+                          uint8_t* bad_status, uint64_t* n_bad)
+{
+    BinView    bv;
+    ZkeyHeader zh;
+    int        rc = zkey_header(ctx, base, size, &bv, &zh);
+    if (rc) return rc;
+    const uint64_t np = zh.n_public, nv = zh.n_vars;
+    if (bv.sec[3].p && bv.sec[3].size < (np + 1) * 64) {
+        ctx->err = "zkey: section shorter than the header implies";
+        return K16_ERR_FORMAT;
+    }
+    PointsStream ps;
+    rc = ps.begin(ctx, PTS_CHUNK_BYTES);
+    static const int hdr_group[6] = {K16_G1, K16_G1, K16_G2, K16_G2, K16_G1, K16_G2};
+    const uint8_t*   h            = zh.pts;
+    for (int i = 0; i < 6 && !rc; i++) {
+        rc = ps.feed(hdr_group[i], h, 1, nullptr, (2ull << 56) | ((uint64_t)i << 2));
+        h += hdr_group[i] == K16_G2 ? 128 : 64;
+    }
+    const struct {
+        uint32_t sec;
+        int      group;
+        uint64_t n;
+    } secs[] = {{3, K16_G1, bv.sec[3].p ? np + 1 : 0}, {5, K16_G1, nv}, {6, K16_G1, nv}, {7, K16_G2, nv},
+                {8, K16_G1, nv - np - 1},          {9, K16_G1, zh.domain_size}};
+    for (const auto& s : secs)
+        if (!rc && s.n) rc = ps.feed(s.group, bv.sec[s.sec].p, s.n, nullptr, (uint64_t)s.sec << 56);
+    uint64_t first = ~0ull, bad = 0;
+    if (!rc) rc = ps.finish(&first, &bad);
+    if (rc) return rc;
+    *n_bad       = bad;
+    *bad_section = bad ? (uint32_t)(first >> 56) : 0;
+    *bad_index   = bad ? (first & ((1ull << 56) - 1)) >> 2 : 0;
+    *bad_status  = bad ? (uint8_t)(first & 3) : 0;
+    return K16_OK;
+}
+
+extern "C" int k16_zkey_check(k16_ctx* ctx, const void* zkey, size_t size, uint32_t* bad_section, uint64_t* bad_index,
+                              uint8_t* bad_status, uint64_t* n_bad)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !zkey || !bad_section || !bad_index || !bad_status || !n_bad) return K16_ERR_ARG;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    return zkey_check_mem(ctx, (const uint8_t*)zkey, size, bad_section, bad_index, bad_status, n_bad);
+    });
+}
+
+extern "C" int k16_zkey_check_file(k16_ctx* ctx, const char* zkey_path, uint32_t* bad_section, uint64_t* bad_index,
+                                   uint8_t* bad_status, uint64_t* n_bad)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !zkey_path || !bad_section || !bad_index || !bad_status || !n_bad) return K16_ERR_ARG;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    MappedFile mf;
+    int        rc = mf.open_ro(zkey_path);
+    if (rc) {
+        ctx->err = std::string("zkey: cannot open/map ") + zkey_path;
+        return rc;
+    }
+    return zkey_check_mem(ctx, mf.base, mf.size, bad_section, bad_index, bad_status, n_bad);
     });
 }
 

@@ -15,6 +15,8 @@
 #include "bn254_pairing.h"
 #include "bn254_fq9.h"
 #include "verify_script.h"
+#include "bn254_points.h"
+#include "points_check.h"
 
 using namespace k16;
 
@@ -36,35 +38,20 @@ struct k16_vk {
     // device buffers of the small-batch (latency) case, allocated once: hipMalloc / hipFree per call cost more than 0.1 ms
     static constexpr uint64_t SMALL_N = 64;
     uint8_t *   d_small_pr = nullptr, *d_small_in = nullptr, *d_small_st = nullptr;
+    // k16_verify_batch_checked, created at its first call: the stream its subgroup check runs on (beside the pairing) and,
+    // for batches up to SMALL_N, a pinned device-mapped buffer for the proofs (SMALL_N x 256 B) and their reasons (SMALL_N B)
+    mutable std::mutex  chk_mu;
+    mutable hipStream_t chk_stream = nullptr;
+    mutable uint8_t *   h_chk = nullptr, *d_chk = nullptr;
 };
 
 namespace {
 
 // Input validation (what ark's deserialisation does before verify_proof ever sees a point; round-2 advisor finding): every
 // coordinate must be a canonical field element (< p: otherwise A, A + p, A + 2p ... would be 2-3 encodings of one proof),
-// and A, C must lie on y^2 = x^3 + 3, B on the twist y^2 = x^3 + 3 / (9 + u).  The all-zero encoding of the point at
-// infinity passes (the pair then contributes 1).  A proof that fails is REJECTED (flag 0).  Membership of B in the
-// r-torsion subgroup is still the caller's duty (include/k16.h).
-__device__ __forceinline__ bool fq_canonical(const Fq& x)
-{
-    uint32_t borrow = 0; // x - p borrows  <=>  x < p
-#pragma unroll
-    for (int i = 0; i < 8; i++) borrow = (uint32_t)(((uint64_t)x.v[i] - FqParams::P[i] - borrow) >> 63);
-    return borrow != 0;
-}
-__device__ __forceinline__ bool g1_input_ok(const G1Aff& a)
-{
-    if (!fq_canonical(a.x) || !fq_canonical(a.y)) return false;
-    if (a.is_zero()) return true;
-    const Fq three = fadd(fadd(Fq::one(), Fq::one()), Fq::one());
-    return fsqr(a.y) == fadd(fmul(fsqr(a.x), a.x), three);
-}
-__device__ __forceinline__ bool g2_input_ok(const G2Aff& b, const Fq2& twist_b)
-{
-    if (!fq_canonical(b.x.a) || !fq_canonical(b.x.b) || !fq_canonical(b.y.a) || !fq_canonical(b.y.b)) return false;
-    if (b.is_zero()) return true;
-    return fsqr(b.y) == fadd(fmul(fsqr(b.x), b.x), twist_b);
-}
+// and A, C must lie on y^2 = x^3 + 3, B on the twist y^2 = x^3 + 3 / (9 + u) -- fq_canonical, g1_input_ok, g2_input_ok of
+// bn254_points.h.  The all-zero encoding of the point at infinity passes (the pair then contributes 1).  A proof that fails
+// is REJECTED (flag 0).  Membership of B in G2 is what k16_verify_batch_checked adds (points_check.hip).
 
 // proof i: A (64 B) | B (128 B) | C (64 B), affine Montgomery.  Writes the three (P, Q) pairs of the check.
 __global__ void __launch_bounds__(64) k_verify_prepare(const uint8_t* __restrict__ proofs, const uint8_t* __restrict__ inputs,
@@ -528,6 +515,8 @@ extern "C" void k16_vk_destroy(k16_vk* vk)
                     vk->d_wtab, vk->d_target, vk->d_small_pr, vk->d_small_in, vk->d_small_st};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    if (vk->chk_stream) (void)hipStreamDestroy(vk->chk_stream);
+    if (vk->h_chk) (void)hipHostFree(vk->h_chk);
     delete vk;
     });
 }
@@ -844,6 +833,73 @@ extern "C" int k16_verify_batch(k16_ctx* ctx, const k16_vk* vk, const void* h_pr
     if (rc) return rc;
     K16_HIP(ctx, hipMemcpyAsync(h_ok, d_ok, n, hipMemcpyDeviceToHost, st));
     K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+    });
+}
+
+namespace k16 {
+const G2Consts& g2_consts_host()
+{
+    static std::once_flag once;
+    static G2Consts       k;
+    std::call_once(once, []() {
+        PairConsts K;
+        pairing_consts_init(&K);
+        k = G2Consts{K.twist_b, K.twqx, K.twqy};
+    });
+    return k;
+}
+} // namespace k16
+
+// k16_verify_batch plus the subgroup test of every B (ark's validated deserialisation).  The check of the whole batch is ONE
+// launch (k_proofs_check, a lane pair per proof) on the key's own stream, issued before k16_verify_batch enqueues the
+// pairing on the context's stream: the two run side by side, and the flags of k16_verify_batch are not touched.
+extern "C" int k16_verify_batch_checked(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                                        uint8_t* h_ok, uint8_t* h_reason)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !vk || vk->ctx != ctx || (n && (!h_proofs || !h_ok)) || (n && vk->n_ic > 1 && !h_inputs)) return K16_ERR_ARG;
+    if (n == 0) return K16_OK;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    const bool                   small = n <= k16_vk::SMALL_N;
+    std::unique_lock<std::mutex> lock(vk->chk_mu);
+    if (!vk->chk_stream) K16_HIP(ctx, hipStreamCreateWithFlags(&vk->chk_stream, hipStreamNonBlocking));
+    if (small && !vk->h_chk) {
+        K16_HIP(ctx, hipHostMalloc((void**)&vk->h_chk, k16_vk::SMALL_N * 257, hipHostMallocMapped | hipHostMallocCoherent));
+        K16_HIP(ctx, hipHostGetDevicePointer((void**)&vk->d_chk, vk->h_chk, 0));
+    }
+    if (!small) lock.unlock(); // (the small buffer is the only state a call keeps between the launch and the read-back)
+    hipStream_t          cs = vk->chk_stream;
+    DevBufs              tmp;
+    uint8_t *            d_pr = nullptr, *d_re = nullptr;
+    std::vector<uint8_t> reason(n);
+    if (small) { // the latency case: no copy commands, the kernel reads the proofs and writes the reasons through the mapping
+        memcpy(vk->h_chk, h_proofs, (size_t)n * 256);
+        d_pr = vk->d_chk;
+        d_re = vk->d_chk + k16_vk::SMALL_N * 256;
+    } else {
+        K16_HIP(ctx, tmp.alloc((void**)&d_pr, (size_t)n * 256));
+        K16_HIP(ctx, tmp.alloc((void**)&d_re, n));
+        K16_HIP(ctx, hipMemcpyAsync(d_pr, h_proofs, (size_t)n * 256, hipMemcpyHostToDevice, cs));
+    }
+    int rc = launch_proofs_check(cs, d_pr, n, d_re);
+    if (rc) {
+        ctx->err = "k_proofs_check launch failed";
+        (void)hipStreamSynchronize(cs);
+        return rc;
+    }
+    rc = k16_verify_batch(ctx, vk, h_proofs, h_inputs, n, h_ok);
+    hipError_t e = small ? hipSuccess : hipMemcpyAsync(reason.data(), d_re, n, hipMemcpyDeviceToHost, cs);
+    const hipError_t es = hipStreamSynchronize(cs); // the check's buffers belong to this call: wait for it whatever happened
+    if (rc) return rc;
+    K16_HIP(ctx, e);
+    K16_HIP(ctx, es);
+    if (small) memcpy(reason.data(), vk->h_chk + k16_vk::SMALL_N * 256, n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t r = reason[i] ? reason[i] : (h_ok[i] ? 0 : 4); // 4 = K16_VERIFY_PAIRING_MISMATCH
+        h_ok[i]         = (h_ok[i] && reason[i] == 0) ? 1 : 0;
+        if (h_reason) h_reason[i] = r;
+    }
     return K16_OK;
     });
 }

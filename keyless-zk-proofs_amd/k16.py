@@ -42,6 +42,7 @@ SYMBOLS = [
     "k16_prover_create", "k16_prover_create_mem", "k16_prover_create_shared", "k16_prover_destroy", "k16_prover_info",
     "k16_prover_prove_file", "k16_prover_prove_file_timed", "k16_prover_prove_mem", "k16_prover_compact_buffers", "k16_prover_prove_compact", "k16_fullprover_prove_mem", "k16_fullprover_compact_lease", "k16_fullprover_prove_compact", "k16_fullprover_compact_cancel", "k16_prover_last_h", "k16_prover_warmup_status",
     "k16_vk_create", "k16_vk_destroy", "k16_verify_batch", "k16_verify_coop_gt", "k16_pairing_vec",
+    "k16_points_check", "k16_verify_batch_checked", "k16_zkey_check", "k16_zkey_check_file",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
     "k16_msm_sharded_last_error", "k16_msm_sharded_set_bases", "k16_msm_sharded_set_bases_device", "k16_msm_sharded_run",
     "k16_msm_sharded_run_device", "k16_msm_sharded_set_piece_rows", "k16_msm_sharded_last_ms",
@@ -140,6 +141,10 @@ def load():
     L.k16_verify_batch.argtypes = [vp, vp, vp, vp, u64, vp]
     L.k16_verify_coop_gt.argtypes = [vp, vp, vp, vp, u64, vp]
     L.k16_pairing_vec.argtypes = [vp, vp, vp, u64, vp]
+    L.k16_points_check.argtypes = [vp, i32, vp, u64, vp]
+    L.k16_verify_batch_checked.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.k16_zkey_check.argtypes = [vp, vp, sz, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
+    L.k16_zkey_check_file.argtypes = [vp, C.c_char_p, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
     L.k16_msm_sharded_create.argtypes = [C.POINTER(i32), i32, i32, u64, C.POINTER(vp)]
     L.k16_msm_sharded_destroy.argtypes = [vp]
     L.k16_msm_sharded_destroy.restype = None
@@ -359,6 +364,16 @@ class Context:
         self._chk(self.L.k16_msm_host(self.h, group, _p(bases), _p(scalars), n, _p(x), _p(a)))
         return x.tobytes(), a.tobytes()
 
+    def points_check(self, group, pts):
+        """Status of every encoded point (k16_points_check): pts (n, 64) for G1 / (n, 128) for G2 affine Montgomery, or
+        raw bytes -> (n,) uint8 of PT_OK / PT_NONCANONICAL / PT_OFF_CURVE / PT_NOT_IN_SUBGROUP."""
+        a = np.frombuffer(pts, dtype=np.uint8) if isinstance(pts, (bytes, bytearray)) else np.ascontiguousarray(pts, dtype=np.uint8)
+        n = a.size // AFF_BYTES[group]
+        assert a.size == n * AFF_BYTES[group]
+        st = np.zeros(n, dtype=np.uint8)
+        self._chk(self.L.k16_points_check(self.h, group, _p(a) if n else None, n, _p(st) if n else None))
+        return st
+
     def synth_points(self, group, start, n):
         """Device buffer with (start+i+1)*G, i < n (affine Montgomery)."""
         d = self.alloc(max(n * AFF_BYTES[group], 16))
@@ -535,6 +550,22 @@ class VerifyingKey:
         self.ctx._chk(self.ctx.L.k16_verify_batch(self.ctx.h, self.h, _p(pr), _p(inp) if inp.size else None, n, _p(ok)))
         return [bool(v) for v in ok]
 
+    def verify_batch_checked(self, proofs, inputs):
+        """k16_verify_batch_checked: verify_batch plus the G2 subgroup test of every B.  Returns (flags, reasons): lists of
+        bools and of ints (0 accepted, 1..3 the first failing point's PT_* status, A then B then C, 4 pairing mismatch)."""
+        n = len(proofs)
+        if n == 0:
+            return [], []
+        pr = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8).copy()
+        assert pr.size == 256 * n
+        inp = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for row in inputs for x in row), dtype=np.uint8).copy()
+        assert inp.size == n * (self.n_ic - 1) * 32
+        ok = np.zeros(n, dtype=np.uint8)
+        why = np.zeros(n, dtype=np.uint8)
+        self.ctx._chk(self.ctx.L.k16_verify_batch_checked(self.ctx.h, self.h, _p(pr), _p(inp) if inp.size else None, n,
+                                                          _p(ok), _p(why)))
+        return [bool(v) for v in ok], [int(v) for v in why]
+
     def coop_gt(self, proofs, inputs):
         """The GT value e(A,B) e(vk_x,-gamma) e(C,-delta) of every proof as the wave-cooperative path computes it
         (k16_verify_coop_gt): (n, 384) uint8.  Raises K16Error(ARG) when that path does not apply."""
@@ -549,6 +580,23 @@ class VerifyingKey:
         if self.h:
             self.ctx.L.k16_vk_destroy(self.h)
             self.h = None
+
+
+PT_OK, PT_NONCANONICAL, PT_OFF_CURVE, PT_NOT_IN_SUBGROUP = 0, 1, 2, 3     # include/k16.h K16_PT_*
+VERIFY_PAIRING_MISMATCH = 4
+
+
+def zkey_check(ctx, zkey):
+    """Every point of a Groth16 zkey checked on the GPU (k16_zkey_check / _file).  zkey: bytes-like, or a path.
+    Returns dict(ok, n_bad, section, index, status): the first failure in (section, index) order when n_bad > 0."""
+    sec, idx, st, nb = C.c_uint32(), C.c_uint64(), C.c_uint8(), C.c_uint64()
+    if isinstance(zkey, (str, os.PathLike)):
+        rc = ctx.L.k16_zkey_check_file(ctx.h, os.fsencode(zkey), C.byref(sec), C.byref(idx), C.byref(st), C.byref(nb))
+    else:
+        a = np.frombuffer(zkey, dtype=np.uint8)
+        rc = ctx.L.k16_zkey_check(ctx.h, _p(a), a.size, C.byref(sec), C.byref(idx), C.byref(st), C.byref(nb))
+    ctx._chk(rc)
+    return dict(ok=nb.value == 0, n_bad=nb.value, section=sec.value, index=idx.value, status=st.value)
 
 
 def pairing_vec(ctx, g1, g2):
