@@ -430,6 +430,42 @@ int  k16_points_check(k16_ctx* ctx, int group, const void* h_points, uint64_t n,
  * beside the pairing (the wave-cooperative path for small batches as well as the general one). */
 int  k16_verify_batch_checked(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
                               uint8_t* h_out_ok, uint8_t* h_out_reason);
+/* Folded batch verification: ONE final exponentiation for n proofs -- the small-exponent batch test of Bellare, Garay and
+ * Rabin (the form bellman ships as verify_proofs_batch).  Same inputs and the same out_ok / out_reason as
+ * k16_verify_batch_checked, for bulk verification where nearly every proof is expected to be valid: waves a service
+ * produced itself, re-verification of history under one key.  Single proofs and small waves belong on
+ * k16_verify_batch[_checked]: below K16_VERIFY_FOLD_MIN proofs this call only forwards to k16_verify_batch_checked.
+ *   Per proof (GPU): canonical coordinates, A and C on the curve, B on the twist AND in G2 (not optional: the fold relies on
+ *   e(w A, B) = e(A, B)^w, which the ate Miller loop only promises for B in G2).  A proof that fails gets its reason
+ *   (1..3) and takes no part in the fold; a proof with a zero point takes no part either and is settled by
+ *   k16_verify_batch_checked.
+ *   The fold: a 128-bit weight w_i per proof from the operating system's CSPRNG (getrandom), drawn after the proofs have
+ *   been handed over, never zero; nothing fixes or disables them.  One equation is checked,
+ *       prod_i e(w_i A_i, B_i) * e(S_x, -gamma) * e(S_C, -delta) * e(-s alpha, beta) == 1
+ *       s = sum w_i mod r,  S_C = sum w_i C_i,  S_x = s IC[0] + sum_j (sum_i w_i x_ij mod r) IC[j+1]:
+ *   n + 3 Miller loops, one final exponentiation (on 64 lanes: the wave-cooperative interpreter), one 128-bit G1 scalar
+ *   multiplication per proof and one G1 MSM.  If it holds, every proof that took part is accepted and *out_folded = 1.
+ *   Acceptance is PROBABILISTIC: a batch holding a wrong proof passes with probability about 2^-128.
+ *   If it does not hold, some proof is wrong: the whole batch is verified again by k16_verify_batch_checked for exact flags
+ *   (*out_folded = 0).  A batch with one bad proof therefore costs the fold PLUS k16_verify_batch_checked's time; there is
+ *   no bisection.
+ * A key whose wave-cooperative program is not on the device (K16_VERIFY_NO_COOP, or no room in LDS) forwards every batch
+ * to k16_verify_batch_checked as well: *out_folded tells.
+ * out_reason and out_folded may be NULL.  The call uses the context's MSM queue and stream: same threading rule as k16_msm
+ * on that context, K16_ERR_ARG when k16_msm_pending(ctx) != 0 on entry; lane, window bits and the one-shot MSM settings of
+ * the context are left as they were found. */
+/* Smallest batch that is folded: the smallest measured n from which the fold's p50 stays below k16_verify_batch_checked's for
+ * every larger measured n (tools/bench_verify_fold.py on one MI355X, profiles/verify_fold/bench_verify_fold.json: the fold
+ * takes 26-28 ms whatever n is up to 16 384; the checked call takes 16.1 ms at n = 2048, the last size of its
+ * wave-cooperative path, and 45.8 ms or more from n = 2049 on).  A compile-time constant, not a switch. */
+#define K16_VERIFY_FOLD_MIN 2049
+int  k16_verify_batch_folded(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                             uint8_t* h_out_ok, uint8_t* h_out_reason, uint8_t* out_folded);
+/* parity tests: the fold at ANY n >= 1 under the caller's weights (n x 16 B little-endian; a zero weight drops that proof):
+ * the value V of the left-hand side above after the final exponentiation, 12 x 32 B in the format of k16_pairing_vec.  No
+ * fallback; K16_ERR_ARG when a proof fails the point checks or has a zero point, or when MSMs are pending. */
+int  k16_verify_fold_gt(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                        const void* h_weights, void* h_out_gt);
 /* every point of a Groth16 zkey, in the sections that are present: 2 (alpha1, beta1, beta2, gamma2, delta1, delta2 =
  * indices 0..5), 3 (IC; the prover does not need it and synthetic keys omit it), 5 (A), 6 (B1), 7 (B2), 8 (C), 9 (H).
  * K16_OK with *n_bad = 0 when all pass; otherwise the first failure in (section, index) order and the number of failing

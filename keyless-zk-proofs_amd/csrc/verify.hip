@@ -11,6 +11,8 @@
 #include <string>
 #include <vector>
 #include <mutex>
+#include <errno.h>
+#include <sys/random.h>
 #include "ctx.h"
 #include "bn254_pairing.h"
 #include "bn254_fq9.h"
@@ -43,6 +45,15 @@ struct k16_vk {
     mutable std::mutex  chk_mu;
     mutable hipStream_t chk_stream = nullptr;
     mutable uint8_t *   h_chk = nullptr, *d_chk = nullptr;
+    // k16_verify_batch_folded: host copies of the key's points (S_x and -s alpha are host scalar multiplications), the
+    // G2 sides of the three fixed pairs (-gamma, -delta, beta) and the final-exponentiation program on the device
+    G1Aff               h_alpha;
+    std::vector<G1Aff>  h_ic;
+    G2Aff               h_fixed_q[3];
+    uint64_t*           d_fe_words = nullptr;
+    uint32_t *          d_fe_terms = nullptr, *d_fe_hdr = nullptr, *d_fe_chunks = nullptr;
+    uint32_t            fe_n_chunks = 0, fe_chunk_words = 0, fe_lds_bytes = 0;
+    bool                fold = false;
 };
 
 namespace {
@@ -161,7 +172,10 @@ __device__ __forceinline__ T coop_shfl_down(const T& v, unsigned delta)
 }
 
 // status[i]: 0 rejected, 1 accepted, 2 "not decided here" (vk_x is the point at infinity: the general path decides)
-template <bool DBG>
+// FOLD (k16_verify_batch_folded): the same interpreter behind a short prologue -- no point checks, no vk_x: `proofs` holds
+// the program's inputs, 12 canonical Fq per block (an Fp12 value), `ctab9` the constants the program names, and the
+// program is coop_build_finalexp_program's.  The per-proof instantiations compile none of it.
+template <bool DBG, bool FOLD = false>
 __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* __restrict__ ctab9, const G1Aff* __restrict__ wtab,
                                                     const G1Aff* __restrict__ ic, uint32_t n_ic,
                                                     const uint8_t* __restrict__ proofs, const uint8_t* __restrict__ inputs,
@@ -201,6 +215,21 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
         stage_chunk(0);
     }
     uint32_t undecided = 0;
+    if constexpr (FOLD) {
+        if (!loader) {
+            const uint4* csrc = reinterpret_cast<const uint4*>(ctab9);
+            uint4*       cdst = reinterpret_cast<uint4*>(slots);
+            for (uint32_t k = lane; k < (D.n_const * 9 + 3) / 4; k += 64) cdst[k] = csrc[k];
+        }
+        __syncthreads(); // (the copy above is in whole uint4s: it may run into the first input slot, stored below)
+        if (!loader && lane < COOP_FE_INPUTS) {
+            Fq              v;
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + (pi * COOP_FE_INPUTS + lane) * sizeof(Fq));
+#pragma unroll
+            for (int k = 0; k < 8; k++) v.v[k] = src[k];
+            coop_st9(slots, D.in_base + lane, fq9_from_fq(v));
+        }
+    } else
     if (!loader) {
     // ---- input validation (canonical coordinates, on the curve / the twist): an invalid proof is rejected here
     {
@@ -478,6 +507,82 @@ const CoopProgram* coop_program()
     return prog;
 }
 
+// how k_verify_coop wants a program: per-step headers, and the steps cut into chunks that fit its staging buffer
+struct CoopLayout {
+    std::vector<uint32_t> hdr, chunks;
+    uint32_t              n_chunks = 0, chunk_words = 0, lds_bytes = 0;
+};
+void coop_layout(const CoopProgram* P, CoopLayout* L)
+{
+    // program -> device: words, terms, per-step header (class | longest combination << 8), chunk table
+    const size_t          n_steps = P->step_class.size();
+    std::vector<uint32_t>&hdr = L->hdr, &chunks = L->chunks;
+    hdr.assign(n_steps, 0);
+    chunks.clear();
+    std::vector<uint32_t> step_t0(n_steps, 0), step_nt(n_steps, 0);
+    for (size_t sidx = 0; sidx < n_steps; sidx++) {
+        uint32_t mx = 0, lo = 0xffffffffu, hi = 0;
+        if (P->step_class[sidx] == CS_LIN)
+            for (int l = 0; l < 64; l++) {
+                const uint64_t w = P->words[sidx * 64 + l];
+                if (!(w >> 63)) continue;
+                const uint32_t nt = (uint32_t)((w >> 14) & 0x3f), t0 = (uint32_t)((w >> 20) & 0xffffff);
+                mx = std::max(mx, nt);
+                lo = std::min(lo, t0);
+                hi = std::max(hi, t0 + ((nt + COOP_TRIP - 1) & ~(COOP_TRIP - 1))); // (combinations are padded to whole trips)
+            }
+        hdr[sidx]     = P->step_class[sidx] | (mx << 8);
+        step_t0[sidx] = hi ? lo : 0;
+        step_nt[sidx] = hi ? hi - lo : 0;
+    }
+    uint32_t max_chunk_words = 0;
+    for (size_t s0 = 0; s0 < n_steps;) { // greedy: as many consecutive steps as fit the staging buffer
+        size_t   s1 = s0;
+        uint32_t tlo = 0, thi = 0;
+        bool     have = false;
+        while (s1 < n_steps) {
+            uint32_t nlo = tlo, nhi = thi;
+            bool     nh  = have;
+            if (step_nt[s1]) {
+                nlo = have ? std::min(tlo, step_t0[s1]) : step_t0[s1];
+                nhi = have ? std::max(thi, step_t0[s1] + step_nt[s1]) : step_t0[s1] + step_nt[s1];
+                nh  = true;
+            }
+            const size_t bytes = (s1 + 1 - s0) * 512 + (size_t)(nh ? nhi - nlo : 0) * 4;
+            if (bytes > COOP_CHUNK_BYTES && s1 > s0) break;
+            tlo = nlo, thi = nhi, have = nh;
+            s1++;
+        }
+        chunks.push_back((uint32_t)s0);
+        chunks.push_back((uint32_t)(s1 - s0));
+        chunks.push_back(have ? tlo : 0);
+        chunks.push_back(have ? thi - tlo : 0);
+        max_chunk_words = std::max<uint32_t>(max_chunk_words, (uint32_t)((s1 - s0) * 129 + (have ? thi - tlo : 0) + 8));
+        s0 = s1;
+    }
+    L->n_chunks = (uint32_t)(chunks.size() / 4);
+    L->chunk_words = (max_chunk_words + 3) & ~3u;
+    L->lds_bytes   = (((P->n_slots * 9 + 3) & ~3u) + 2 * L->chunk_words + L->n_chunks * 4) * 4; // two staging halves
+}
+
+const CoopProgram* fold_program()
+{
+    static std::once_flag once;
+    static CoopProgram*   prog = nullptr;
+    std::call_once(once, []() {
+        try {
+            PairConsts K;
+            pairing_consts_init(&K);
+            CoopProgram* p = new CoopProgram();
+            coop_build_finalexp_program(K, p);
+            prog = p;
+        } catch (...) {
+            prog = nullptr;
+        }
+    });
+    return prog;
+}
+
 struct DevBufs {
     std::vector<void*> p;
     ~DevBufs()
@@ -512,7 +617,8 @@ extern "C" void k16_vk_destroy(k16_vk* vk)
     if (!vk) return;
     if (vk->ctx) (void)hipSetDevice(vk->ctx->device);
     void* bufs[] = {vk->d_ic, vk->d_g2, vk->d_K, vk->d_eab, vk->d_words, vk->d_terms, vk->d_hdr, vk->d_chunks, vk->d_ctab9,
-                    vk->d_wtab, vk->d_target, vk->d_small_pr, vk->d_small_in, vk->d_small_st};
+                    vk->d_wtab, vk->d_target, vk->d_small_pr, vk->d_small_in, vk->d_small_st, vk->d_fe_words, vk->d_fe_terms,
+                    vk->d_fe_hdr, vk->d_fe_chunks};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (vk->chk_stream) (void)hipStreamDestroy(vk->chk_stream);
@@ -548,6 +654,12 @@ extern "C" int k16_vk_create(k16_ctx* ctx, const void* alpha1, const void* beta2
     memcpy(&neg[1], delta2, sizeof(G2Aff));
     for (G2Aff& g : neg)
         if (!g.is_zero()) g.y = fneg(g.y);
+    memcpy(&vk->h_alpha, alpha1, sizeof(G1Aff));
+    vk->h_ic.resize(n_ic);
+    memcpy(vk->h_ic.data(), ic, (size_t)n_ic * sizeof(G1Aff));
+    vk->h_fixed_q[0] = neg[0];
+    vk->h_fixed_q[1] = neg[1];
+    memcpy(&vk->h_fixed_q[2], beta2, sizeof(G2Aff));
     hipStream_t st = ctx->stream;
     if ((e = hipMemcpyAsync(vk->d_ic, ic, (size_t)n_ic * sizeof(G1Aff), hipMemcpyHostToDevice, st)) != hipSuccess ||
         (e = hipMemcpyAsync(vk->d_g2, neg, sizeof neg, hipMemcpyHostToDevice, st)) != hipSuccess ||
@@ -601,53 +713,12 @@ extern "C" int k16_vk_create(k16_ctx* ctx, const void* alpha1, const void* beta2
                     wtab[((size_t)j * 64 + w) * 16] = G1Aff{Fq::zero(), Fq::zero()};
                 }
             }
-            // program -> device: words, terms, per-step header (class | longest combination << 8), chunk table
-            const size_t          n_steps = P->step_class.size();
-            std::vector<uint32_t> hdr(n_steps), chunks;
-            std::vector<uint32_t> step_t0(n_steps, 0), step_nt(n_steps, 0);
-            for (size_t sidx = 0; sidx < n_steps; sidx++) {
-                uint32_t mx = 0, lo = 0xffffffffu, hi = 0;
-                if (P->step_class[sidx] == CS_LIN)
-                    for (int l = 0; l < 64; l++) {
-                        const uint64_t w = P->words[sidx * 64 + l];
-                        if (!(w >> 63)) continue;
-                        const uint32_t nt = (uint32_t)((w >> 14) & 0x3f), t0 = (uint32_t)((w >> 20) & 0xffffff);
-                        mx = std::max(mx, nt);
-                        lo = std::min(lo, t0);
-                        hi = std::max(hi, t0 + ((nt + COOP_TRIP - 1) & ~(COOP_TRIP - 1))); // (combinations are padded to whole trips)
-                    }
-                hdr[sidx]     = P->step_class[sidx] | (mx << 8);
-                step_t0[sidx] = hi ? lo : 0;
-                step_nt[sidx] = hi ? hi - lo : 0;
-            }
-            uint32_t max_chunk_words = 0;
-            for (size_t s0 = 0; s0 < n_steps;) { // greedy: as many consecutive steps as fit the staging buffer
-                size_t   s1 = s0;
-                uint32_t tlo = 0, thi = 0;
-                bool     have = false;
-                while (s1 < n_steps) {
-                    uint32_t nlo = tlo, nhi = thi;
-                    bool     nh  = have;
-                    if (step_nt[s1]) {
-                        nlo = have ? std::min(tlo, step_t0[s1]) : step_t0[s1];
-                        nhi = have ? std::max(thi, step_t0[s1] + step_nt[s1]) : step_t0[s1] + step_nt[s1];
-                        nh  = true;
-                    }
-                    const size_t bytes = (s1 + 1 - s0) * 512 + (size_t)(nh ? nhi - nlo : 0) * 4;
-                    if (bytes > COOP_CHUNK_BYTES && s1 > s0) break;
-                    tlo = nlo, thi = nhi, have = nh;
-                    s1++;
-                }
-                chunks.push_back((uint32_t)s0);
-                chunks.push_back((uint32_t)(s1 - s0));
-                chunks.push_back(have ? tlo : 0);
-                chunks.push_back(have ? thi - tlo : 0);
-                max_chunk_words = std::max<uint32_t>(max_chunk_words, (uint32_t)((s1 - s0) * 129 + (have ? thi - tlo : 0) + 8));
-                s0 = s1;
-            }
-            vk->n_chunks  = (uint32_t)(chunks.size() / 4);
-            vk->chunk_words = (max_chunk_words + 3) & ~3u;
-            vk->lds_bytes   = (((P->n_slots * 9 + 3) & ~3u) + 2 * vk->chunk_words + vk->n_chunks * 4) * 4; // two staging halves
+            CoopLayout lay;
+            coop_layout(P, &lay);
+            const std::vector<uint32_t>&hdr = lay.hdr, &chunks = lay.chunks;
+            vk->n_chunks    = lay.n_chunks;
+            vk->chunk_words = lay.chunk_words;
+            vk->lds_bytes   = lay.lds_bytes;
             const Fq2* ev = &eab.c0.c0;
             Fq         target[12];
             for (int i = 0; i < 6; i++) {
@@ -674,6 +745,23 @@ extern "C" int k16_vk_create(k16_ctx* ctx, const void* alpha1, const void* beta2
                        hipFuncSetAttribute((const void*)k_verify_coop<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)vk->lds_bytes) == hipSuccess;
             if (!vk->coop) (void)hipGetLastError();
+            // the folded verifier's single final exponentiation: a second program for the same interpreter
+            const CoopProgram* F = fold_program();
+            if (vk->coop && F) {
+                CoopLayout fl;
+                coop_layout(F, &fl);
+                vk->fe_n_chunks    = fl.n_chunks;
+                vk->fe_chunk_words = fl.chunk_words;
+                vk->fe_lds_bytes   = fl.lds_bytes;
+                vk->fold = vk->fe_lds_bytes + static_lds <= 160 * 1024 &&
+                           up((void**)&vk->d_fe_words, F->words.data(), F->words.size() * 8) &&
+                           up((void**)&vk->d_fe_terms, F->terms.data(), F->terms.size() * 4) &&
+                           up((void**)&vk->d_fe_hdr, fl.hdr.data(), fl.hdr.size() * 4) &&
+                           up((void**)&vk->d_fe_chunks, fl.chunks.data(), fl.chunks.size() * 4) &&
+                           hipFuncSetAttribute((const void*)k_verify_coop<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)vk->fe_lds_bytes) == hipSuccess;
+                if (!vk->fold) (void)hipGetLastError();
+            }
         }
     }
     *out = vk;
@@ -931,6 +1019,403 @@ extern "C" int k16_pairing_vec(k16_ctx* ctx, const void* h_g1, const void* h_g2,
     if (rc) return rc;
     K16_HIP(ctx, hipMemcpyAsync(h_out_gt, d_gt, n * sizeof(Fp12), hipMemcpyDeviceToHost, st));
     K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Folded batch verification (k16_verify_batch_folded): the small-exponent batch test of Bellare, Garay and Rabin, in the
+// form bellman ships as verify_proofs_batch.  With a random 128-bit weight w_i per proof, ONE equation
+//     prod_i e(w_i A_i, B_i) * e(S_x, -gamma) * e(S_C, -delta) * e(-s alpha, beta) == 1
+//     s = sum w_i mod r,  S_C = sum w_i C_i,  S_x = s IC[0] + sum_j (sum_i w_i x_ij mod r) IC[j+1]
+// holds when every proof is valid, and with probability about 2^-128 otherwise: n + 3 Miller loops and one final
+// exponentiation instead of 3n and n.  e(w A, B) = e(A, B)^w needs B in G2, so the subgroup test is part of it.
+namespace {
+
+constexpr uint8_t FOLD_ZERO_POINT = 0x80; // status of a proof left to the per-proof path: A, B or C is the point at infinity
+
+// One lane per proof.  reason[i] (k_proofs_check) != 0, a zero point or a zero weight leave the proof out: its pair, its C
+// row and its Fr row are all zero, so it contributes 1 / nothing.  Otherwise P = w A (affine), Q = B, the MSM row (C, w)
+// and fr[0][i] = w, fr[j][i] = w x_ij mod r (standard form; x_ij is any 256-bit integer and acts modulo r).
+__global__ void __launch_bounds__(64) k_fold_prepare(const uint8_t* __restrict__ proofs, const uint8_t* __restrict__ inputs,
+                                                     const uint8_t* __restrict__ weights, const uint8_t* __restrict__ reason,
+                                                     uint64_t n, uint32_t n_ic, G1Aff* __restrict__ P, G2Aff* __restrict__ Q,
+                                                     G1Aff* __restrict__ Cb, uint32_t* __restrict__ scal, Fr* __restrict__ fr,
+                                                     uint8_t* __restrict__ status)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* pr = proofs + i * 256;
+    G1Aff a, c;
+    G2Aff b;
+    memcpy(&a, pr, 64);
+    memcpy(&b, pr + 64, 128);
+    memcpy(&c, pr + 192, 64);
+    uint32_t w[4];
+    memcpy(w, weights + i * 16, 16);
+    const uint8_t re   = reason[i];
+    const bool    zero = a.is_zero() || b.is_zero() || c.is_zero();
+    status[i]          = re ? re : (zero ? FOLD_ZERO_POINT : 0);
+    const bool in      = !re && !zero && (w[0] | w[1] | w[2] | w[3]) != 0;
+    Fr         wf      = Fr::zero();
+    G1Aff      wa      = G1Aff{Fq::zero(), Fq::zero()};
+    if (in) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) wf.v[k] = w[k];
+        // w A: 128-bit double-and-add, most significant bit first.  0 < w < r and A has order r: never the point at infinity
+        G1Xyzz acc = G1Xyzz::zero();
+#pragma clang loop unroll(disable)
+        for (int bit = 127; bit >= 0; bit--) {
+            acc = pdbl(acc);
+            if ((w[bit >> 5] >> (bit & 31)) & 1u) acc = padd_mixed(acc, a);
+        }
+        const Fq t = finv(fmul(acc.zz, acc.zzz)); // 1 / zz = t zzz, 1 / zzz = t zz
+        wa         = G1Aff{fmul(acc.x, fmul(t, acc.zzz)), fmul(acc.y, fmul(t, acc.zz))};
+    } else {
+        b = G2Aff{Fq2::zero(), Fq2::zero()};
+        c = G1Aff{Fq::zero(), Fq::zero()};
+    }
+    P[i]  = wa;
+    Q[i]  = b;
+    Cb[i] = c;
+#pragma unroll
+    for (int k = 0; k < 8; k++) scal[i * 8 + k] = k < 4 ? wf.v[k] : 0u;
+    fr[i] = wf;
+    const Fr wm = to_mont(wf);
+#pragma clang loop unroll(disable)
+    for (uint32_t j = 1; j < n_ic; j++) {
+        Fr x;
+        memcpy(&x, inputs + (i * (n_ic - 1) + (j - 1)) * 32, 32);
+#pragma clang loop unroll(disable)
+        for (int k = 0; k < 5; k++) cond_sub_p<FrParams>(x.v); // 2^256 < 6r
+        fr[(uint64_t)j * n + i] = fmul(wm, x);                  // (w R)(x) / R
+    }
+}
+
+// sums in Fr: column j of `in` (m values) -> gridDim.x partial sums per column; FR_SUM_CHUNK values per block
+constexpr uint32_t FR_SUM_CHUNK = 2048;
+__global__ void __launch_bounds__(256) k_fold_fr_sum(const Fr* __restrict__ in, uint64_t m, Fr* __restrict__ out)
+{
+    __shared__ Fr  sh[256];
+    const uint64_t lo = (uint64_t)blockIdx.x * FR_SUM_CHUNK, hi = lo + FR_SUM_CHUNK < m ? lo + FR_SUM_CHUNK : m;
+    const Fr*      col = in + (uint64_t)blockIdx.y * m;
+    Fr             acc = Fr::zero();
+    for (uint64_t k = lo + threadIdx.x; k < hi; k += 256) acc = fadd(acc, col[k]);
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (unsigned d = 128; d >= 1; d >>= 1) {
+        if (threadIdx.x < d) sh[threadIdx.x] = fadd(sh[threadIdx.x], sh[threadIdx.x + d]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+}
+
+// product in Fp12: block b multiplies in[b * FP12_PROD_CHUNK ...) down to out[b].  One wavefront: every lane multiplies its
+// strided share, then a tree over LDS.  The field is commutative: any association order gives the same canonical bytes.
+constexpr uint32_t FP12_PROD_CHUNK = 256;
+__global__ void __launch_bounds__(64) k_fp12_product(const Fp12* __restrict__ in, uint64_t m, Fp12* __restrict__ out)
+{
+    __shared__ Fp12 sh[64];
+    const uint64_t  lo = (uint64_t)blockIdx.x * FP12_PROD_CHUNK, hi = lo + FP12_PROD_CHUNK < m ? lo + FP12_PROD_CHUNK : m;
+    Fp12            acc = f12_one();
+    bool            have = false;
+#pragma clang loop unroll(disable)
+    for (uint64_t k = lo + threadIdx.x; k < hi; k += 64) {
+        Fp12 t = in[k];
+        if (have)
+            f12_mul(&acc, &acc, &t);
+        else
+            acc = t;
+        have = true;
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+#pragma clang loop unroll(disable)
+    for (unsigned d = 32; d >= 1; d >>= 1) {
+        if (threadIdx.x < d && lo + threadIdx.x + d < hi) { // (lanes past the end of the chunk hold 1: skipped)
+            Fp12 t = sh[threadIdx.x + d];
+            f12_mul(&acc, &acc, &t);
+            sh[threadIdx.x] = acc;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
+// the context's one-shot MSM state and lane, put back when the fold is done (a prover may share the context)
+struct MsmStateGuard {
+    k16_ctx*        c;
+    int             lane, derive_lane, reuse_sort_lane;
+    unsigned        forced_c;
+    bool            reuse_sort, graphs_on;
+    const uint64_t *skip_next, *acc_skip_next;
+    const uint32_t* remap_next;
+    const void*     hs[3];
+    explicit MsmStateGuard(k16_ctx* cx)
+        : c(cx), lane(cx->cur_lane), derive_lane(cx->derive_lane), reuse_sort_lane(cx->reuse_sort_lane), forced_c(cx->forced_c),
+          reuse_sort(cx->reuse_sort), graphs_on(cx->graphs_on), skip_next(cx->skip_next), acc_skip_next(cx->acc_skip_next),
+          remap_next(cx->remap_next)
+    {
+        for (int k = 0; k < 3; k++) hs[k] = cx->hs_next[k];
+        c->cur_lane = 0; // lane 0's stream is the context's stream: the MSM is ordered behind k_fold_prepare
+        c->forced_c = 0;
+        c->graphs_on = false;
+        c->derive_lane = c->reuse_sort_lane = -1;
+        c->reuse_sort = false;
+        c->skip_next = c->acc_skip_next = nullptr;
+        c->remap_next = nullptr;
+        c->hs_next[0] = c->hs_next[1] = c->hs_next[2] = nullptr;
+    }
+    ~MsmStateGuard()
+    {
+        c->cur_lane = lane;
+        c->forced_c = forced_c;
+        c->graphs_on = graphs_on;
+        c->derive_lane = derive_lane;
+        c->reuse_sort_lane = reuse_sort_lane;
+        c->reuse_sort = reuse_sort;
+        c->skip_next = skip_next;
+        c->acc_skip_next = acc_skip_next;
+        c->remap_next = remap_next;
+        for (int k = 0; k < 3; k++) c->hs_next[k] = hs[k];
+        // the bucket sort this MSM left in lane 0's workspace is of scalars that are about to be freed
+        c->lanes[0].sorted_scalars = nullptr;
+        c->lanes[0].sorted_n       = 0;
+    }
+};
+
+// The fold of n proofs under the given weights: V (after the final exponentiation) to h_gt, the per-proof status
+// (0 took part, 1..3 failed a point check, FOLD_ZERO_POINT has a zero point) to h_status.
+int fold_run(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n, const uint8_t* h_weights,
+             uint8_t* h_status, Fp12* h_gt)
+{
+    hipStream_t    st   = ctx->stream;
+    const uint32_t n_ic = vk->n_ic;
+    DevBufs        tmp;
+    uint8_t *      d_pr = nullptr, *d_in = nullptr, *d_w = nullptr, *d_re = nullptr, *d_st = nullptr;
+    G1Aff *        d_P = nullptr, *d_C = nullptr;
+    G2Aff*         d_Q = nullptr;
+    uint32_t*      d_scal = nullptr;
+    Fr *           d_fr = nullptr, *d_fr2 = nullptr;
+    Fp12 *         d_f = nullptr, *d_g = nullptr;
+    const size_t   in_bytes = (size_t)n * (n_ic - 1) * 32;
+    const uint64_t m = n + 3; // pairs
+    auto passes_total = [](uint64_t cnt, uint64_t chunk) { // results of every pass of a tree that ends at one value
+        uint64_t total = 0;
+        do {
+            cnt = (cnt + chunk - 1) / chunk;
+            total += cnt;
+        } while (cnt > 1);
+        return total;
+    };
+    K16_HIP(ctx, tmp.alloc((void**)&d_pr, (size_t)n * 256));
+    K16_HIP(ctx, tmp.alloc((void**)&d_in, in_bytes));
+    K16_HIP(ctx, tmp.alloc((void**)&d_w, (size_t)n * 16));
+    K16_HIP(ctx, tmp.alloc((void**)&d_re, n));
+    K16_HIP(ctx, tmp.alloc((void**)&d_st, n));
+    K16_HIP(ctx, tmp.alloc((void**)&d_P, (size_t)m * sizeof(G1Aff)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_Q, (size_t)m * sizeof(G2Aff)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_C, (size_t)n * sizeof(G1Aff)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_scal, (size_t)n * 32));
+    K16_HIP(ctx, tmp.alloc((void**)&d_fr, (size_t)n * n_ic * sizeof(Fr)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_fr2, (size_t)passes_total(n, FR_SUM_CHUNK) * n_ic * sizeof(Fr)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_f, (size_t)m * sizeof(Fp12)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_g, (size_t)passes_total(m, FP12_PROD_CHUNK) * sizeof(Fp12)));
+    K16_HIP(ctx, hipMemcpyAsync(d_pr, h_proofs, (size_t)n * 256, hipMemcpyHostToDevice, st));
+    if (in_bytes) K16_HIP(ctx, hipMemcpyAsync(d_in, h_inputs, in_bytes, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_w, h_weights, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    {
+        k16_stat_scope sc(ctx, "fold_prepare");
+        int rc = launch_proofs_check(st, d_pr, n, d_re);
+        if (rc) {
+            ctx->err = "k_proofs_check launch failed";
+            return rc;
+        }
+        hipLaunchKernelGGL(k_fold_prepare, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, d_pr, d_in, d_w, d_re, n, n_ic, d_P, d_Q,
+                           d_C, d_scal, d_fr, d_st);
+        K16_HIP(ctx, hipGetLastError());
+    }
+    // s, t_j: tree sums in Fr
+    const Fr* d_sums = d_fr;
+    {
+        k16_stat_scope sc(ctx, "fold_reduce");
+        uint64_t       cnt = n;
+        Fr*            dst = d_fr2;
+        while (cnt > 1 || d_sums == d_fr) {
+            const uint64_t parts = (cnt + FR_SUM_CHUNK - 1) / FR_SUM_CHUNK;
+            hipLaunchKernelGGL(k_fold_fr_sum, dim3((unsigned)parts, n_ic), dim3(256), 0, st, d_sums, cnt, dst);
+            d_sums = dst;
+            dst += parts * n_ic;
+            cnt = parts;
+        }
+        K16_HIP(ctx, hipGetLastError());
+    }
+    std::vector<Fr> sums(n_ic);
+    K16_HIP(ctx, hipMemcpyAsync(sums.data(), d_sums, (size_t)n_ic * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipMemcpyAsync(h_status, d_st, n, hipMemcpyDeviceToHost, st));
+    // S_C = sum w_i C_i: the context's G1 MSM over the device rows (synchronises the stream: the sums above have arrived)
+    G1Aff pts[3];
+    {
+        MsmStateGuard g(ctx);
+        int           rc = k16_msm(ctx, K16_G1, d_C, d_scal, n, nullptr, &pts[1]);
+        if (rc) return rc;
+    }
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    // S_x and -s alpha: n_ic + 1 scalar multiplications on the host (~0.1 ms each; one GPU lane would need ~5 ms)
+    {
+        G1Xyzz sx = G1Xyzz::zero();
+        for (uint32_t j = 0; j < n_ic; j++)
+            sx = padd(sx, pmul_scalar(G1Xyzz::from_aff(vk->h_ic[j]), reinterpret_cast<const uint8_t*>(sums[j].v)));
+        pts[0] = to_affine(sx);
+        pts[2] = to_affine(pneg(pmul_scalar(G1Xyzz::from_aff(vk->h_alpha), reinterpret_cast<const uint8_t*>(sums[0].v))));
+    }
+    K16_HIP(ctx, hipMemcpyAsync(d_P + n, pts, sizeof pts, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_Q + n, vk->h_fixed_q, sizeof vk->h_fixed_q, hipMemcpyHostToDevice, st));
+    {
+        k16_stat_scope sc(ctx, "fold_miller");
+        hipLaunchKernelGGL(k_pair_miller, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, d_P, d_Q, m, vk->d_K, d_f);
+        K16_HIP(ctx, hipGetLastError());
+    }
+    const Fp12* d_val = d_f;
+    {
+        k16_stat_scope sc(ctx, "fold_product");
+        uint64_t       cnt = m;
+        Fp12*          dst = d_g;
+        while (cnt > 1) { // (every pass writes behind the previous one's results)
+            const uint64_t parts = (cnt + FP12_PROD_CHUNK - 1) / FP12_PROD_CHUNK;
+            hipLaunchKernelGGL(k_fp12_product, dim3((unsigned)parts), dim3(64), 0, st, d_val, cnt, dst);
+            d_val = dst;
+            dst += parts;
+            cnt = parts;
+        }
+        K16_HIP(ctx, hipGetLastError());
+    }
+    // the ONE final exponentiation, on 64 lanes: the recorded program on the wave-cooperative interpreter
+    Fq* d_gt = nullptr;
+    K16_HIP(ctx, tmp.alloc((void**)&d_gt, 12 * sizeof(Fq)));
+    {
+        const CoopProgram* F = fold_program();
+        CoopDev            D;
+        D.words = vk->d_fe_words;
+        D.terms = vk->d_fe_terms;
+        D.hdr = vk->d_fe_hdr;
+        D.chunks = vk->d_fe_chunks;
+        D.n_chunks = vk->fe_n_chunks;
+        D.chunk_words = vk->fe_chunk_words;
+        D.n_const = F->n_const;
+        D.in_base = F->in_base;
+        D.n_slots = F->n_slots;
+        D.target_const = 0;
+        for (int i = 0; i < 12; i++) D.out_slot[i] = F->out_slot[i];
+        k16_stat_scope sc(ctx, "fold_finalexp");
+        // (status and target are the per-proof kernel's: the flag it writes, into this call's d_re, is not read -- V is compared on the host)
+        hipLaunchKernelGGL((k_verify_coop<false, true>), dim3(1), dim3(128), vk->fe_lds_bytes, st, D, vk->d_ctab9, (const G1Aff*)nullptr,
+                           (const G1Aff*)nullptr, 0u, reinterpret_cast<const uint8_t*>(d_val), (const uint8_t*)nullptr, vk->d_target, d_re,
+                           d_gt, (uint64_t*)nullptr, (const Fq2*)nullptr);
+        K16_HIP(ctx, hipGetLastError());
+    }
+    K16_HIP(ctx, hipMemcpyAsync(h_gt, d_gt, sizeof(Fp12), hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+int fold_args_ok(k16_ctx* ctx, const k16_vk* vk)
+{
+    if (k16_msm_pending(ctx) != 0) {
+        ctx->err = "folded verification uses the context's MSM queue: finish the MSMs in flight first (k16_msm_pending != 0)";
+        return K16_ERR_ARG;
+    }
+    return K16_OK;
+}
+
+} // namespace
+
+// parity tests: the fold's value V under the caller's weights (n x 16 B little-endian; zero drops the proof), 12 x 32 B in
+// the format of k16_pairing_vec.  No fallback; K16_ERR_ARG when a proof fails the point checks or has a zero point.
+extern "C" int k16_verify_fold_gt(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                                  const void* h_weights, void* h_out_gt)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !vk || vk->ctx != ctx || !n || !h_proofs || !h_weights || !h_out_gt || (vk->n_ic > 1 && !h_inputs)) return K16_ERR_ARG;
+    if (!vk->fold) {
+        ctx->err = "k16_verify_fold_gt: the wave-cooperative interpreter is not available for this key";
+        return K16_ERR_ARG;
+    }
+    if (n > (1ull << 24)) return K16_ERR_ARG;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = fold_args_ok(ctx, vk);
+    if (rc) return rc;
+    std::vector<uint8_t> status(n);
+    Fp12                 v;
+    rc = fold_run(ctx, vk, h_proofs, h_inputs, n, (const uint8_t*)h_weights, status.data(), &v);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < n; i++)
+        if (status[i]) {
+            ctx->err = "k16_verify_fold_gt: proof " + std::to_string(i) + (status[i] == FOLD_ZERO_POINT ? " has a zero point" : " fails the point checks");
+            return K16_ERR_ARG;
+        }
+    memcpy(h_out_gt, &v, sizeof v);
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_verify_batch_folded(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                                       uint8_t* h_ok, uint8_t* h_reason, uint8_t* out_folded)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (out_folded) *out_folded = 0;
+    if (!ctx || !vk || vk->ctx != ctx || (n && (!h_proofs || !h_ok)) || (n && vk->n_ic > 1 && !h_inputs)) return K16_ERR_ARG;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = fold_args_ok(ctx, vk);
+    if (rc) return rc;
+    // small batches, and keys without the interpreter: the per-proof path (same flags and reasons)
+    if (n < K16_VERIFY_FOLD_MIN || n > (1ull << 24) || !vk->fold) return k16_verify_batch_checked(ctx, vk, h_proofs, h_inputs, n, h_ok, h_reason);
+    // the weights: drawn from the operating system AFTER the proofs are in our hands, never zero
+    std::vector<uint8_t> w((size_t)n * 16);
+    for (size_t got = 0; got < w.size();) {
+        const ssize_t k = getrandom(w.data() + got, std::min<size_t>(w.size() - got, 1u << 20), 0);
+        if (k < 0) {
+            if (errno == EINTR) continue;
+            ctx->err = "k16_verify_batch_folded: getrandom failed";
+            return K16_ERR_IO;
+        }
+        got += (size_t)k;
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        bool z = true;
+        for (int k = 0; k < 16; k++) z = z && w[i * 16 + k] == 0;
+        if (z) w[i * 16] = 1;
+    }
+    std::vector<uint8_t> status(n);
+    Fp12                 v;
+    rc = fold_run(ctx, vk, h_proofs, h_inputs, n, w.data(), status.data(), &v);
+    if (rc) return rc;
+    if (!f12_eq(v, f12_one())) // some proof that took part is wrong: the per-proof path names it
+        return k16_verify_batch_checked(ctx, vk, h_proofs, h_inputs, n, h_ok, h_reason);
+    // every proof that took part is accepted; one that failed a point check has its reason; one with a zero point is
+    // settled by the per-proof path
+    std::vector<uint64_t> rest;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t s = status[i];
+        h_ok[i]         = s == 0;
+        if (h_reason) h_reason[i] = s == FOLD_ZERO_POINT ? 0 : s;
+        if (s == FOLD_ZERO_POINT) rest.push_back(i);
+    }
+    if (!rest.empty()) {
+        const size_t         ib = (size_t)(vk->n_ic - 1) * 32;
+        std::vector<uint8_t> pr(rest.size() * 256), in(rest.size() * ib + 1), ok(rest.size()), re(rest.size());
+        for (size_t k = 0; k < rest.size(); k++) {
+            memcpy(&pr[k * 256], (const uint8_t*)h_proofs + rest[k] * 256, 256);
+            if (ib) memcpy(&in[k * ib], (const uint8_t*)h_inputs + rest[k] * ib, ib);
+        }
+        rc = k16_verify_batch_checked(ctx, vk, pr.data(), in.data(), rest.size(), ok.data(), re.data());
+        if (rc) return rc;
+        for (size_t k = 0; k < rest.size(); k++) {
+            h_ok[rest[k]] = ok[k];
+            if (h_reason) h_reason[rest[k]] = re[k];
+        }
+    }
+    if (out_folded) *out_folded = 1;
     return K16_OK;
     });
 }

@@ -277,115 +277,11 @@ inline void coop_const_table(const PairConsts& K, const Fp12& eab, const std::ve
 static_assert(COOP_MAX_COEF * 5 < (1 << 15), "linear step: the 2^15 p bias must cover the negative part of a combination");
 static_assert(COOP_MAX_TERMS < 64, "linear step: 6-bit term count");
 static_assert((COOP_TRIP_TERMS & (COOP_TRIP_TERMS - 1)) == 0, "linear step: terms per trip must be a power of two");
-// Builds the program.  Depends only on the curve constants' zero / one pattern (K), not on a key.
-inline void coop_build_program(const PairConsts& K, CoopProgram* P)
+// The back end shared by every program: from the recorded graph B and the 12 nodes of the result to steps, slots and
+// instruction words.  P->in_base is set by the caller; the n_inputs slots from there are the program's inputs.
+inline void coop_compile(k16t::Builder& B, const int32_t out_node[12], uint32_t n_inputs, CoopProgram* P)
 {
     namespace t = k16t;
-    t::Builder B;
-    t::cur() = &B;
-    struct Reset {
-        ~Reset() { t::cur() = nullptr; }
-    } reset;
-    const uint32_t n_lines = coop_line_count();
-    // ---- constants and inputs are N_IN nodes; node id -> slot
-    std::vector<int32_t> slot_of_in; // per N_IN node
-    auto new_in = [&](int32_t slot) {
-        int32_t id = B.add_node(t::N_IN, slot, -1);
-        return t::Fq{id};
-    };
-    B.zero_id = new_in(0).id;
-    B.one_id  = new_in(1).id;
-    Fq pc[COOP_NPC];
-    coop_flatten_consts(K, pc);
-    uint32_t next = 2;
-    auto     cst = [&](const Fq& concrete) -> t::Fq { // a constant slot; known zeros / ones fold
-        const uint32_t s = next++;
-        if (concrete.is_zero()) return t::Fq::zero();
-        if (concrete == Fq::one()) return t::Fq::one();
-        return new_in((int32_t)s);
-    };
-    t::PairConsts TK;
-    {
-        uint32_t n  = 0;
-        auto     g2 = [&]() {
-            t::Fq a = cst(pc[n]), b = cst(pc[n + 1]);
-            n += 2;
-            return t::Fq2{a, b};
-        };
-        TK.twist_b = g2();
-        TK.twqx    = g2();
-        TK.twqy    = g2();
-        for (int k = 0; k < 4; k++) TK.frob6_c1[k] = g2();
-        for (int k = 0; k < 4; k++) TK.frob6_c2[k] = g2();
-        for (int k = 0; k < 4; k++) TK.frob12_c1[k] = g2();
-        TK.two_inv = cst(pc[n]);
-    }
-    P->target_const = next;
-    next += 12;
-    const uint32_t line_base = next;
-    next += 2 * n_lines * 6;
-    P->n_const = next;
-    P->n_lines = n_lines;
-    P->in_base = next;
-    auto inp = [&](uint32_t k) { return new_in((int32_t)(P->in_base + k)); };
-    // vk_x comes in PROJECTIVE form (XYZZ: x = X / ZZ, y = Y / ZZZ), as sx = X ZZZ, sy = Y ZZ, sz = ZZ ZZZ: its lines are
-    // evaluated scaled by sz, (c0 sy, c1 sx, c2 sz) instead of (c0 y, c1 x, c2).  The factor is in Fq, so the final
-    // exponentiation removes it ((p - 1) divides (p^12 - 1) / r) -- and the prologue needs no inversion for vk_x.
-    t::Aff<t::Fq>  pa{inp(0), inp(1)}, pc3{inp(6), inp(7)};
-    const t::Fq    vk_sx = inp(8), vk_sy = inp(9), vk_sz = inp(10);
-    t::Aff<t::Fq2> qb{t::Fq2{inp(2), inp(3)}, t::Fq2{inp(4), inp(5)}};
-    next += COOP_N_INPUTS;
-    auto line = [&](uint32_t pair /* 1 or 2 */, uint32_t k) {
-        const uint32_t s = line_base + ((pair - 1) * n_lines + k) * 6;
-        t::Ell         l;
-        l.c0 = t::Fq2{new_in((int32_t)s), new_in((int32_t)s + 1)};
-        l.c1 = t::Fq2{new_in((int32_t)s + 2), new_in((int32_t)s + 3)};
-        l.c2 = t::Fq2{new_in((int32_t)s + 4), new_in((int32_t)s + 5)};
-        return l;
-    };
-    // ---- the multi-Miller loop (ark-ec Bn::multi_miller_loop): one squaring per digit for all three pairs
-    t::Fp12        f = t::f12_one();
-    t::G2Hom       r{qb.x, qb.y, t::Fq2::one()};
-    t::Aff<t::Fq2> nq{qb.x, t::fneg(qb.y)};
-    t::Ell         l;
-    uint32_t       k = 0;
-    auto ells = [&]() { // the three line evaluations of one step; the fixed pairs first: their operands are ready early
-        {
-            const t::Ell l1 = line(1, k);
-            t::Fq2       c0 = t::fmul_fp(l1.c0, vk_sy), c1 = t::fmul_fp(l1.c1, vk_sx), c2 = t::fmul_fp(l1.c2, vk_sz);
-            t::f12_mul_by_034(&f, &c0, &c1, &c2);
-        }
-        t::f12_ell(&f, line(2, k), pc3);
-        t::f12_ell(&f, l, pa);
-        k++;
-    };
-    for (int i = (int)ATE_TOP; i >= 1; i--) {
-        if (i != (int)ATE_TOP) t::f12_sqr(&f, &f);
-        t::g2hom_double(&r, &l, &TK);
-        ells();
-        const unsigned d = (unsigned)(i - 1);
-        if ((ATE_NZ_LO >> d) & 1) {
-            t::g2hom_add(&r, ((ATE_NEG_LO >> d) & 1) ? &nq : &qb, &l);
-            ells();
-        }
-    }
-    t::Aff<t::Fq2> q1 = t::g2_mul_by_char(qb, TK);
-    t::Aff<t::Fq2> q2 = t::g2_mul_by_char(q1, TK);
-    q2.y              = t::fneg(q2.y);
-    t::g2hom_add(&r, &q1, &l);
-    ells();
-    t::g2hom_add(&r, &q2, &l);
-    ells();
-    if (k != n_lines) throw std::logic_error("coop program: line count");
-    t::Fp12 e;
-    (void)t::final_exponentiation(&e, &f, &TK);
-    const t::Fq2* ev = &e.c0.c0;
-    int32_t       out_node[12];
-    for (int i = 0; i < 6; i++) {
-        out_node[2 * i]     = ev[i].a.id;
-        out_node[2 * i + 1] = ev[i].b.id;
-    }
-
     // ---- reachability
     const int32_t        N = (int32_t)B.nodes.size();
     std::vector<uint8_t> live(N, 0);
@@ -579,7 +475,7 @@ inline void coop_build_program(const PairConsts& K, CoopProgram* P)
     std::vector<int32_t>              slot(ops.size(), -1);
     std::vector<int32_t>              free_slots;
     std::vector<std::vector<int32_t>> expire(n_steps + 2);
-    uint32_t                          next_slot = P->in_base + COOP_N_INPUTS;
+    uint32_t                          next_slot = P->in_base + n_inputs;
     auto node_slot = [&](int32_t v) -> uint32_t {
         if (B.nodes[v].op == t::N_IN) return (uint32_t)B.nodes[v].a;
         return (uint32_t)slot[op_of[v]];
@@ -633,6 +529,177 @@ inline void coop_build_program(const PairConsts& K, CoopProgram* P)
     P->n_slots = next_slot;
     if (next_slot >= (1u << 14) || P->terms.size() >= (1u << 24)) throw std::logic_error("coop program: encoding overflow");
     for (int i = 0; i < 12; i++) P->out_slot[i] = node_slot(out_node[i]);
+}
+
+// Builds the program.  Depends only on the curve constants' zero / one pattern (K), not on a key.
+inline void coop_build_program(const PairConsts& K, CoopProgram* P)
+{
+    namespace t = k16t;
+    t::Builder B;
+    t::cur() = &B;
+    struct Reset {
+        ~Reset() { t::cur() = nullptr; }
+    } reset;
+    const uint32_t n_lines = coop_line_count();
+    // ---- constants and inputs are N_IN nodes; node id -> slot
+    std::vector<int32_t> slot_of_in; // per N_IN node
+    auto new_in = [&](int32_t slot) {
+        int32_t id = B.add_node(t::N_IN, slot, -1);
+        return t::Fq{id};
+    };
+    B.zero_id = new_in(0).id;
+    B.one_id  = new_in(1).id;
+    Fq pc[COOP_NPC];
+    coop_flatten_consts(K, pc);
+    uint32_t next = 2;
+    auto     cst = [&](const Fq& concrete) -> t::Fq { // a constant slot; known zeros / ones fold
+        const uint32_t s = next++;
+        if (concrete.is_zero()) return t::Fq::zero();
+        if (concrete == Fq::one()) return t::Fq::one();
+        return new_in((int32_t)s);
+    };
+    t::PairConsts TK;
+    {
+        uint32_t n  = 0;
+        auto     g2 = [&]() {
+            t::Fq a = cst(pc[n]), b = cst(pc[n + 1]);
+            n += 2;
+            return t::Fq2{a, b};
+        };
+        TK.twist_b = g2();
+        TK.twqx    = g2();
+        TK.twqy    = g2();
+        for (int k = 0; k < 4; k++) TK.frob6_c1[k] = g2();
+        for (int k = 0; k < 4; k++) TK.frob6_c2[k] = g2();
+        for (int k = 0; k < 4; k++) TK.frob12_c1[k] = g2();
+        TK.two_inv = cst(pc[n]);
+    }
+    P->target_const = next;
+    next += 12;
+    const uint32_t line_base = next;
+    next += 2 * n_lines * 6;
+    P->n_const = next;
+    P->n_lines = n_lines;
+    P->in_base = next;
+    auto inp = [&](uint32_t k) { return new_in((int32_t)(P->in_base + k)); };
+    // vk_x comes in PROJECTIVE form (XYZZ: x = X / ZZ, y = Y / ZZZ), as sx = X ZZZ, sy = Y ZZ, sz = ZZ ZZZ: its lines are
+    // evaluated scaled by sz, (c0 sy, c1 sx, c2 sz) instead of (c0 y, c1 x, c2).  The factor is in Fq, so the final
+    // exponentiation removes it ((p - 1) divides (p^12 - 1) / r) -- and the prologue needs no inversion for vk_x.
+    t::Aff<t::Fq>  pa{inp(0), inp(1)}, pc3{inp(6), inp(7)};
+    const t::Fq    vk_sx = inp(8), vk_sy = inp(9), vk_sz = inp(10);
+    t::Aff<t::Fq2> qb{t::Fq2{inp(2), inp(3)}, t::Fq2{inp(4), inp(5)}};
+    next += COOP_N_INPUTS;
+    auto line = [&](uint32_t pair /* 1 or 2 */, uint32_t k) {
+        const uint32_t s = line_base + ((pair - 1) * n_lines + k) * 6;
+        t::Ell         l;
+        l.c0 = t::Fq2{new_in((int32_t)s), new_in((int32_t)s + 1)};
+        l.c1 = t::Fq2{new_in((int32_t)s + 2), new_in((int32_t)s + 3)};
+        l.c2 = t::Fq2{new_in((int32_t)s + 4), new_in((int32_t)s + 5)};
+        return l;
+    };
+    // ---- the multi-Miller loop (ark-ec Bn::multi_miller_loop): one squaring per digit for all three pairs
+    t::Fp12        f = t::f12_one();
+    t::G2Hom       r{qb.x, qb.y, t::Fq2::one()};
+    t::Aff<t::Fq2> nq{qb.x, t::fneg(qb.y)};
+    t::Ell         l;
+    uint32_t       k = 0;
+    auto ells = [&]() { // the three line evaluations of one step; the fixed pairs first: their operands are ready early
+        {
+            const t::Ell l1 = line(1, k);
+            t::Fq2       c0 = t::fmul_fp(l1.c0, vk_sy), c1 = t::fmul_fp(l1.c1, vk_sx), c2 = t::fmul_fp(l1.c2, vk_sz);
+            t::f12_mul_by_034(&f, &c0, &c1, &c2);
+        }
+        t::f12_ell(&f, line(2, k), pc3);
+        t::f12_ell(&f, l, pa);
+        k++;
+    };
+    for (int i = (int)ATE_TOP; i >= 1; i--) {
+        if (i != (int)ATE_TOP) t::f12_sqr(&f, &f);
+        t::g2hom_double(&r, &l, &TK);
+        ells();
+        const unsigned d = (unsigned)(i - 1);
+        if ((ATE_NZ_LO >> d) & 1) {
+            t::g2hom_add(&r, ((ATE_NEG_LO >> d) & 1) ? &nq : &qb, &l);
+            ells();
+        }
+    }
+    t::Aff<t::Fq2> q1 = t::g2_mul_by_char(qb, TK);
+    t::Aff<t::Fq2> q2 = t::g2_mul_by_char(q1, TK);
+    q2.y              = t::fneg(q2.y);
+    t::g2hom_add(&r, &q1, &l);
+    ells();
+    t::g2hom_add(&r, &q2, &l);
+    ells();
+    if (k != n_lines) throw std::logic_error("coop program: line count");
+    t::Fp12 e;
+    (void)t::final_exponentiation(&e, &f, &TK);
+    const t::Fq2* ev = &e.c0.c0;
+    int32_t       out_node[12];
+    for (int i = 0; i < 6; i++) {
+        out_node[2 * i]     = ev[i].a.id;
+        out_node[2 * i + 1] = ev[i].b.id;
+    }
+
+    coop_compile(B, out_node, COOP_N_INPUTS, P);
+}
+
+// The fold's program (k16_verify_batch_folded, verify_fold.hip): ONE final exponentiation.  Inputs: the 12 Fq of an Fp12
+// value (c0.c0.a first); output: final_exponentiation of it.  Its constant slots are the first COOP_FE_NCONST of the
+// per-proof program's table (zero, one, PairConsts), so any key's table serves.
+constexpr uint32_t COOP_FE_NCONST = 2 + COOP_NPC;
+constexpr uint32_t COOP_FE_INPUTS = 12;
+inline void coop_build_finalexp_program(const PairConsts& K, CoopProgram* P)
+{
+    namespace t = k16t;
+    t::Builder B;
+    t::cur() = &B;
+    struct Reset {
+        ~Reset() { t::cur() = nullptr; }
+    } reset;
+    auto new_in = [&](int32_t slot) { return t::Fq{B.add_node(t::N_IN, slot, -1)}; };
+    B.zero_id = new_in(0).id;
+    B.one_id  = new_in(1).id;
+    Fq pc[COOP_NPC];
+    coop_flatten_consts(K, pc);
+    uint32_t next = 2;
+    auto     cst = [&](const Fq& concrete) -> t::Fq { // as in coop_build_program: known zeros / ones fold
+        const uint32_t s = next++;
+        if (concrete.is_zero()) return t::Fq::zero();
+        if (concrete == Fq::one()) return t::Fq::one();
+        return new_in((int32_t)s);
+    };
+    t::PairConsts TK;
+    {
+        uint32_t n  = 0;
+        auto     g2 = [&]() {
+            t::Fq a = cst(pc[n]), b = cst(pc[n + 1]);
+            n += 2;
+            return t::Fq2{a, b};
+        };
+        TK.twist_b = g2();
+        TK.twqx    = g2();
+        TK.twqy    = g2();
+        for (int k = 0; k < 4; k++) TK.frob6_c1[k] = g2();
+        for (int k = 0; k < 4; k++) TK.frob6_c2[k] = g2();
+        for (int k = 0; k < 4; k++) TK.frob12_c1[k] = g2();
+        TK.two_inv = cst(pc[n]);
+    }
+    if (next != COOP_FE_NCONST) throw std::logic_error("coop program: constant count");
+    P->n_const = P->in_base = next;
+    P->n_lines = 0;
+    P->target_const = 0; // (no target among the constants: the caller compares)
+    t::Fp12  f;
+    t::Fq2*  fv = &f.c0.c0;
+    for (int i = 0; i < 6; i++) fv[i] = t::Fq2{new_in((int32_t)(P->in_base + 2 * i)), new_in((int32_t)(P->in_base + 2 * i + 1))};
+    t::Fp12 e;
+    (void)t::final_exponentiation(&e, &f, &TK);
+    const t::Fq2* ev = &e.c0.c0;
+    int32_t       out_node[12];
+    for (int i = 0; i < 6; i++) {
+        out_node[2 * i]     = ev[i].a.id;
+        out_node[2 * i + 1] = ev[i].b.id;
+    }
+    coop_compile(B, out_node, COOP_FE_INPUTS, P);
 }
 
 // ------------------------------------------------------------------------------------------------ host interpreter

@@ -43,6 +43,7 @@ SYMBOLS = [
     "k16_prover_prove_file", "k16_prover_prove_file_timed", "k16_prover_prove_mem", "k16_prover_compact_buffers", "k16_prover_prove_compact", "k16_fullprover_prove_mem", "k16_fullprover_compact_lease", "k16_fullprover_prove_compact", "k16_fullprover_compact_cancel", "k16_prover_last_h", "k16_prover_warmup_status",
     "k16_vk_create", "k16_vk_destroy", "k16_verify_batch", "k16_verify_coop_gt", "k16_pairing_vec",
     "k16_points_check", "k16_verify_batch_checked", "k16_zkey_check", "k16_zkey_check_file",
+    "k16_verify_batch_folded", "k16_verify_fold_gt",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
     "k16_msm_sharded_last_error", "k16_msm_sharded_set_bases", "k16_msm_sharded_set_bases_device", "k16_msm_sharded_run",
     "k16_msm_sharded_run_device", "k16_msm_sharded_set_piece_rows", "k16_msm_sharded_last_ms",
@@ -143,6 +144,8 @@ def load():
     L.k16_pairing_vec.argtypes = [vp, vp, vp, u64, vp]
     L.k16_points_check.argtypes = [vp, i32, vp, u64, vp]
     L.k16_verify_batch_checked.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.k16_verify_batch_folded.argtypes = [vp, vp, vp, vp, u64, vp, vp, C.POINTER(C.c_uint8)]
+    L.k16_verify_fold_gt.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.k16_zkey_check.argtypes = [vp, vp, sz, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
     L.k16_zkey_check_file.argtypes = [vp, C.c_char_p, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
     L.k16_msm_sharded_create.argtypes = [C.POINTER(i32), i32, i32, u64, C.POINTER(vp)]
@@ -566,6 +569,39 @@ class VerifyingKey:
                                                           _p(ok), _p(why)))
         return [bool(v) for v in ok], [int(v) for v in why]
 
+    def verify_batch_folded(self, proofs, inputs):
+        """k16_verify_batch_folded: the small-exponent batch test -- one final exponentiation for the whole batch, random
+        128-bit weights drawn by the library.  Same flags and reasons as verify_batch_checked (a wrong proof slips through
+        with probability ~2^-128).  Returns (flags, reasons, folded): folded is True when the fold itself decided the
+        batch, False when the call went through the per-proof path (batch below VERIFY_FOLD_MIN, or a wrong proof in it)."""
+        n = len(proofs)
+        if n == 0:
+            return [], [], False
+        pr = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8).copy()
+        assert pr.size == 256 * n
+        inp = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for row in inputs for x in row), dtype=np.uint8).copy()
+        assert inp.size == n * (self.n_ic - 1) * 32
+        ok = np.zeros(n, dtype=np.uint8)
+        why = np.zeros(n, dtype=np.uint8)
+        folded = C.c_uint8(0)
+        self.ctx._chk(self.ctx.L.k16_verify_batch_folded(self.ctx.h, self.h, _p(pr), _p(inp) if inp.size else None, n,
+                                                         _p(ok), _p(why), C.byref(folded)))
+        return [bool(v) for v in ok], [int(v) for v in why], bool(folded.value)
+
+    def fold_gt(self, proofs, inputs, weights):
+        """The value of the fold's left-hand side after the final exponentiation under the caller's weights (ints below
+        2^128; zero drops the proof), k16_verify_fold_gt: 384 bytes in the format of Context.pairing_vec.  Raises
+        K16Error(ARG) when a proof fails the point checks or has a zero point."""
+        n = len(proofs)
+        pr = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8).copy()
+        assert pr.size == 256 * n and len(weights) == n
+        inp = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for row in inputs for x in row), dtype=np.uint8).copy()
+        assert inp.size == n * (self.n_ic - 1) * 32
+        w = np.frombuffer(b"".join(int(x).to_bytes(16, "little") for x in weights), dtype=np.uint8).copy()
+        out = np.zeros(384, dtype=np.uint8)
+        self.ctx._chk(self.ctx.L.k16_verify_fold_gt(self.ctx.h, self.h, _p(pr), _p(inp) if inp.size else None, n, _p(w), _p(out)))
+        return out.tobytes()
+
     def coop_gt(self, proofs, inputs):
         """The GT value e(A,B) e(vk_x,-gamma) e(C,-delta) of every proof as the wave-cooperative path computes it
         (k16_verify_coop_gt): (n, 384) uint8.  Raises K16Error(ARG) when that path does not apply."""
@@ -584,6 +620,7 @@ class VerifyingKey:
 
 PT_OK, PT_NONCANONICAL, PT_OFF_CURVE, PT_NOT_IN_SUBGROUP = 0, 1, 2, 3     # include/k16.h K16_PT_*
 VERIFY_PAIRING_MISMATCH = 4
+VERIFY_FOLD_MIN = 2049                                                     # include/k16.h K16_VERIFY_FOLD_MIN
 
 
 def zkey_check(ctx, zkey):
