@@ -1017,10 +1017,7 @@ def test_compact_witness_upload_edge_cases(tmp_path, monkeypatch, n_vars):
         for name, w in cases.items():
             w[0] = 0
             w[0, 0] = 1
-            with open(wt, "wb") as fh:
-                import struct
-                sec1 = struct.pack("<I", 32) + pm.limbs(pm.R) + struct.pack("<I", n_vars)
-                fh.write(b"wtns" + struct.pack("<II", 2, 2) + zb._section(1, sec1) + zb._section(2, w.tobytes()))
+            zb.write_wtns(wt, w)
             want, h_ref = ol.prove_files(zk, wt, r, s, nthreads=8, want_h=True)
             got = p.prove_mem(w, r, s)
             assert np.array_equal(p.last_h(), h_ref), name
@@ -1066,10 +1063,7 @@ def test_compact_witness_hand_off(tmp_path):
                     np.frombuffer(pm.limbs(256 + k), dtype=np.uint8)
             w[0] = 0
             w[0, 0] = 1
-            import struct
-            with open(wt, "wb") as fh:
-                sec1 = struct.pack("<I", 32) + pm.limbs(pm.R) + struct.pack("<I", n_vars)
-                fh.write(b"wtns" + struct.pack("<II", 2, 2) + zb._section(1, sec1) + zb._section(2, w.tobytes()))
+            zb.write_wtns(wt, w)
             want, h_ref = ol.prove_files(zk, wt, r, s, nthreads=8, want_h=True)
             n_wide = _fill_compact(p, w)
             assert n_wide == n_wide_target
@@ -1111,8 +1105,7 @@ def test_compact_witness_hand_off(tmp_path):
         wfull[:, 1] |= 1                                 # every wire >= 256: more wide values than the lists hold
         wfull[0] = 0
         wfull[0, 0] = 1
-        with open(wt, "wb") as fh:
-            fh.write(b"wtns" + struct.pack("<II", 2, 2) + zb._section(1, sec1) + zb._section(2, wfull.tobytes()))
+        zb.write_wtns(wt, wfull)
         assert p.prove_mem(wfull, r, s) == ol.prove_files(zk, wt, r, s, nthreads=8)
         p.close()
         # a small circuit uploads plainly: no compact buffers
