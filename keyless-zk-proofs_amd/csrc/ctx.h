@@ -20,6 +20,16 @@
 
 #include "host_pool.h"
 
+// Wave priority of the polynomial chain's kernels.  3 (above everything) until round 6; the witness MSMs' short kernels run at 3
+// too and their accumulations at 0.  With the chain at 1 it still wins against the accumulations it runs beside, but the
+// witness MSMs' fold / weighted-sum tails -- whose end, not the chain's, is what the H accumulation's start waits for -- are no
+// longer held up by NTT waves: p50 over 11 alternating runs on two boxes 5.35-5.57 (median 5.46) against 5.37-5.84 (5.67) ms, equal on
+// a third, two provers unchanged (profiles/r06/ab_wave_priorities.log, ab_chain_priority_second_box.log).  -DK16_CHAIN_PRIO=n to compare
+// (defined here, once, for ntt.hip and prover.hip: a build with the macro on one unit only would mix priorities).
+#ifndef K16_CHAIN_PRIO
+#define K16_CHAIN_PRIO 1
+#endif
+
 struct k16_devbuf {
     void*  p     = nullptr;
     size_t bytes = 0;
@@ -38,32 +48,26 @@ struct k16_ntt_table {
     // transform uses root(s', j) = roots[j << (s - s')] for j < 2^(s'-1) -- consecutive butterflies read entries 2^(s - s')
     // apart, a 36-byte gather with a stride of 72 B ... 1.1 KB over a 151 MB table (4 M loads per 2^21 transform, as many bytes
     // as the data itself).  stage9 holds root(s', j) at entry 2^(s'-1) - 2^16 + j for 17 <= s' < s: 32 consecutive butterflies
-    // read 1152 contiguous bytes.  Null for tables below 2^18 or with K16_NTT_NO_STAGE_TABLES.
+    // read 1152 contiguous bytes.  Null for tables below 2^18.
     uint32_t* stage9 = nullptr;
     k16::Fr   pow2inv[34];
     k16::Fq9  pow2inv9[34];     // 2^-k as Fr9
 };
 
-// Every environment switch of the library, read ONCE when a context is created (k16_ctx_create) and
-// kept in the context: no getenv on any per-MSM, per-transform or per-proof path (getenv races with a host program's setenv
-// and costs a lock per call), and an object made from a context (prover, verifying key) sees the values its context was made
-// with.  All of these select between code paths that give the SAME results (alternative / reference implementations kept
-// parity-tested, rejected scheduling experiments kept so that they can be re-measured) or switch diagnostics on.  Switches
-// that change a RESULT on purpose (measurement probes, fault injection) do not exist in libk16.so: they are compiled only
-// into the lab / testing builds (-DK16_LAB, -DK16_TESTING).
+// The environment switches of the HIP units, read ONCE, in k16_tuning::from_env, when a context is
+// created (k16_ctx_create) and kept in the context: no getenv on any per-MSM, per-transform or per-proof path (getenv races
+// with a host program's setenv and costs a lock per call), and an object made from a context (prover, verifying key) sees
+// the values its context was made with.  Each of them is used by a test, forces a path that is live for other inputs
+// (atomic_sort: the generic sort of every MSM above 2^24 points; seg), selects an implementation that is also reachable
+// through the C ABI (classes, b_sort, b_derive, b2_first, fused_hscalars), or switches a diagnostic on.  All of them select
+// between code paths that give the SAME results.  Switches that change a RESULT on purpose (measurement probes, fault
+// injection) do not exist in libk16.so: they are compiled only into the lab / testing builds (-DK16_LAB, -DK16_TESTING).
+// (The size of the process's host thread pool, K16_HOST_THREADS, belongs to no context: k16_ctx_pool reads it once.)
 struct k16_tuning {
-    bool     atomic_sort = false, no_fused_convert = false, no_staged_sort = false, fused_bins = false, x8 = false;
-    bool     no_l1_prefetch = false, ntt_tail_small = false, ntt_unfused = false, ntt_no_stage_tables = false;
-    bool     no_fixed_base = false, no_stream_priority = false, b_sort = false, b_derive = false, no_skip_zero_rows = false;
-    bool     classes = false, no_warmup = false, spmv_full = false, fused_hscalars = false, no_split_classes = false;
-    bool     b2_first = false, no_acc_skip = false;
-    // round 6 scheduling experiments (identical results): lane of the H MSM (default 1, behind C's MSM), lane of
-    // the B1 MSM (default 0, behind A's), the H MSM's wait for the chain issued behind its sort's memset instead of in front
-    int      g2_acc_split = 1; // lane pairs per segment in the witness MSMs' G2 accumulation (1, 2 or 4; msm_kernels.inc k_accumulate_split)
-    int      h_lane = 1, b1_lane = 0, witness_seg = 0; // witness_seg: segment length of the witness MSMs' accumulations (default 32)
-    bool     h_wait_first = false;
+    bool     atomic_sort = false, b_sort = false, b_derive = false, classes = false, no_warmup = false, fused_hscalars = false;
+    bool     b2_first = false;
     bool     trace = false, trace_enq = false, trace_host = false, verify_no_coop = false, verify_coop_trace = false;
-    int      seg = 0, wsum_mlog = -1, witness_c = 0, ntt_tile_log = 0, narrow_chain = 0, narrow_chain_g2 = 0;
+    int      seg = 0;
     uint64_t verify_coop_max = 2048;
     static k16_tuning from_env();
 };
@@ -89,7 +93,7 @@ struct k16_ctx {
     static constexpr int N_LANES = 4;
     struct Lane {
         hipStream_t stream = nullptr;
-        k16_devbuf  ws_counts, ws_offsets, ws_cursor, ws_sorted, ws_segoff, ws_segbucket, ws_partial, ws_big, ws_misc,
+        k16_devbuf  ws_counts, ws_offsets, ws_cursor, ws_sorted, ws_segoff, ws_segbucket, ws_partial, ws_big,
             ws_lvl_a, ws_lvl_b, ws_lvl_c, ws_lvl_d, ws_scan, ws_conv, ws_narrow;
         // bucket sort still valid in this lane's workspace (same scalars, n, c): see reuse_sort
         // hipGraph replay of the launch-bound parts of an MSM (see graphs_on): key -> state / executable graph
@@ -102,8 +106,6 @@ struct k16_ctx {
         uint64_t                       graphs_gen = 0; // workspace generation the cached graphs were captured for
         hipEvent_t  sort_done = nullptr; // recorded on `stream` after every bucket sort (cross-lane reuse waits on it)
         hipEvent_t  acc_done  = nullptr; // recorded after every bucket accumulation (see serialize_acc)
-        hipEvent_t  lvl1_done = nullptr; // ... after the first level of the weighted bucket sum, and after the whole
-        hipEvent_t  tail_done = nullptr; //     reduction (see acc_fence_mode)
         const void* sorted_scalars = nullptr;
         uint64_t    sorted_n = 0;
         unsigned    sorted_c = 0;
@@ -114,7 +116,6 @@ struct k16_ctx {
     int  cur_lane = 0; // lane of the next k16_msm_enqueue*
     std::vector<hipStream_t> placeholder_streams; // k16_ctx_create_ex: created before the context's own, destroyed with it
     bool yielding_waits = false; // K16_OPT_YIELDING_WAITS: host waits poll + sleep instead of spinning inside the runtime (k16_event_wait)
-    hipEvent_t wait_after_memset = nullptr; // one-shot: the next bucket sort waits for this event BEHIND its tables' memset
     void* pinned = nullptr;     // small pinned host staging buffer (coherent, mapped into the device's address space)
     void* pinned_dev = nullptr; // its device-side address: the last kernel of an MSM writes its <= 240 partial sums straight
                                 // into the staging slot (a hipMemcpyAsync D2H was observed to BLOCK the enqueuing thread for
@@ -177,38 +178,21 @@ struct k16_ctx {
     int             derive_lane   = -1; // next enqueue: bucket lists of its own from that lane's partition, minus skip_next's rows
     // workgroups of a 1024-element NTT pass per CU (ntt.hip): 4 is what fits; 3 (K16_OPT_SHARED_GPU) leaves registers for a wave of
     // another prover's bucket accumulation beside them
-    unsigned        ntt_wg_per_cu = 4, ntt_wg_per_cu_default = 4;
+    unsigned        ntt_wg_per_cu = 4;
     // next enqueue: its scalars do not exist yet -- scalar i = fromMontgomery(hs_next[0][i] * hs_next[1][i] - hs_next[2][i]) over Fr
     // (packed R' values), formed by the sort's counting pass and written to d_scalars (the prover's H MSM, groth16.cpp:266-283)
     const void*     hs_next[3]    = {nullptr, nullptr, nullptr};
-    // K16_SERIALIZE_ACC=1 (bench.py sets it): a lane's bucket accumulation waits for the previous lane's.  Two of these
-    // chip-filling kernels never overlap anyway (kernel traces: the second starts when the first ends), so nothing is
-    // lost, but the HIP events that time the kernel on its own stream then bracket its execution only -- without the fence
-    // the interval also contains the time the launch sits behind the other lane's accumulation.
+    // K16_OPT_PIPELINED_MSM (k16_ctx_set_option; bench.py's MSM loop sets it): a lane's bucket accumulation waits for the
+    // previous lane's (last_acc_done).  Two of these chip-filling kernels never overlap anyway (kernel traces: the second starts
+    // when the first ends), so nothing is lost, but the HIP events that time the kernel on its own stream then bracket its
+    // execution only -- without the fence the interval also contains the time the launch sits behind the other lane's
+    // accumulation.
     bool        serialize_acc = false;
-    // slots per lane of the first weighted-sum level are capped at 2^wsum_mlog_cap: 8 (3) gives the shortest single MSM;
-    // 16 (4) does 12 % less reduction work with chains twice as long -- +5 % for pipelined MSMs, +4 % latency for one
-    unsigned    wsum_mlog_cap = 3;
     hipEvent_t  last_acc_done = nullptr;
-    // what a lane's accumulation waits for when serialize_acc is on: 0 the previous MSM's accumulation, 1 its first
-    // weighted-sum level (the previous tail's fold + level 1 run alone, its bit sums beside this accumulation), 2 its whole
-    // reduction.  A chip-filling accumulation starves every kernel of the other lanes that starts beside it (kernel traces:
-    // a fold launched next to an accumulation ends when the accumulation ends), so with mode 0 the tails of ALL queued MSMs
-    // wait for ALL queued accumulations.
-    int         acc_fence_mode = 0;
-    hipEvent_t  last_lvl1_done = nullptr, last_tail_done = nullptr;
-
-    // Unused dynamic LDS requested for the bucket accumulation, to cap ITS occupancy (K16_ACC_LDS, bytes per 128-thread
-    // workgroup: 36864 -> 4 workgroups = 2 waves/SIMD per CU instead of the 3 its 159 VGPRs allow).  The registers a
-    // third wave would take stay free for the other lanes' sort / fold / reduction kernels, which otherwise wait for a
-    // whole accumulate workgroup to retire before one of their waves fits.
-    unsigned    acc_lds_bytes = 0;
-    unsigned    acc_grid_cap  = 0; // K16_ACC_GRID: at most this many (persistent, grid-stride) accumulate workgroups
-    // every kernel of the bucket sort in <= 32 VGPRs, so that it is resident BESIDE another lane's bucket accumulation
-    // (msm_kernels.inc, "lean sort"); set with K16_OPT_PIPELINED_MSM, or K16_LEAN_SORT=0/1
-    bool        lean_sort     = false;
-    bool        wc_sort       = false; // K16_WC_SORT: write-combining scatter pass of the partition (k_part_wc)
-    unsigned    acc_dyn_grid  = 0; // K16_ACC_DYN: persistent accumulate grid of this many workgroups with dynamic chunk fetch
+    // slots per lane of the first weighted-sum level are capped at 2^wsum_mlog_cap: 8 (3) gives the shortest single MSM;
+    // 16 (4, set with K16_OPT_PIPELINED_MSM) does 12 % less reduction work with chains twice as long -- +5 % for pipelined
+    // MSMs, +4 % latency for one
+    unsigned    wsum_mlog_cap = 3;
 
     std::map<uint32_t, k16_ntt_table> ntt_tables;
     // the per-window combine of an MSM's partial sums runs on the host pool only when asked to (the prover does for the H MSM,

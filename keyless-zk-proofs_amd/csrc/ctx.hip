@@ -60,44 +60,19 @@ k16_tuning k16_tuning::from_env()
     k16_tuning t;
     auto on  = [](const char* n) { return getenv(n) != nullptr; };
     auto onv = [](const char* n) { const char* e = getenv(n); return e && atoi(e) != 0; };
-    auto num = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
     t.atomic_sort        = on("K16_ATOMIC_SORT");
-    t.no_fused_convert   = on("K16_NO_FUSED_CONVERT");
-    t.no_staged_sort     = on("K16_NO_STAGED_SORT");
-    t.fused_bins         = on("K16_FUSED_BINS");
-    t.x8                 = on("K16_X8");
-    t.no_l1_prefetch     = on("K16_NO_L1_PREFETCH");
-    t.ntt_tail_small     = on("K16_NTT_TAIL_SMALL");
-    t.ntt_unfused        = on("K16_NTT_UNFUSED");
-    t.ntt_no_stage_tables = on("K16_NTT_NO_STAGE_TABLES");
-    t.no_fixed_base      = on("K16_NO_FIXED_BASE");
-    t.no_stream_priority = on("K16_NO_STREAM_PRIORITY");
     t.b_sort             = onv("K16_B_SORT");
     t.b_derive           = onv("K16_B_DERIVE");
-    t.no_skip_zero_rows  = on("K16_NO_SKIP_ZERO_ROWS");
     t.classes            = onv("K16_CLASSES");
     t.no_warmup          = on("K16_NO_WARMUP");
-    t.spmv_full          = on("K16_SPMV_FULL");
     t.fused_hscalars     = on("K16_FUSED_HSCALARS");
-    t.no_split_classes   = on("K16_NO_SPLIT_CLASSES");
     t.b2_first           = on("K16_B2_FIRST");
-    t.no_acc_skip        = on("K16_NO_ACC_SKIP");
-    t.h_lane             = std::max(1, std::min(k16_ctx::N_LANES - 1, num("K16_H_LANE", 1)));
-    t.b1_lane            = std::max(0, std::min(k16_ctx::N_LANES - 1, num("K16_B1_LANE", 0)));
-    t.h_wait_first       = onv("K16_H_WAIT_FIRST");
-    t.g2_acc_split       = num("K16_G2_ACC_SPLIT", 1);
-    t.witness_seg        = std::max(0, std::min(1024, num("K16_WITNESS_SEG", 0)));
     t.trace              = on("K16_TRACE");
     t.trace_enq          = on("K16_TRACE_ENQ");
     t.trace_host         = on("K16_TRACE_HOST");
     t.verify_no_coop     = on("K16_VERIFY_NO_COOP");
     t.verify_coop_trace  = on("K16_VERIFY_COOP_TRACE");
-    t.seg                = num("K16_SEG", 0);
-    t.wsum_mlog          = num("K16_WSUM_MLOG", -1);
-    t.witness_c          = num("K16_WITNESS_C", 0);
-    t.ntt_tile_log       = num("K16_NTT_TILE_LOG", 0);
-    t.narrow_chain       = num("K16_NARROW_CHAIN", 0);
-    t.narrow_chain_g2    = num("K16_NARROW_CHAIN_G2", 0);
+    if (const char* e = getenv("K16_SEG")) t.seg = atoi(e);
     if (const char* e = getenv("K16_VERIFY_COOP_MAX")) t.verify_coop_max = strtoull(e, nullptr, 10);
     return t;
 }
@@ -116,43 +91,17 @@ extern "C" int k16_ctx_create_ex(int device, int stream_offset, k16_ctx** out)
     k16_ctx* c = new k16_ctx();
     c->device  = device;
     c->tune    = k16_tuning::from_env(); // the only place the library reads its tuning switches
-    // placeholder streams first (k16_ctx_create_ex; K16_STREAM_SKEW=a[,b] adds (a * n + b) mod 8 for the n-th context of the process:
-    // the round-6 experiment switch): they shift the hardware queues -- and so the dispatch pipes -- this context's
-    // streams land on relative to the contexts made before it
-    {
-        int skew = stream_offset & 7;
-        if (const char* e = getenv("K16_STREAM_SKEW")) {
-            static std::atomic<int> n_ctx{0};
-            const char* comma = strchr(e, ',');
-            skew = (skew + n_ctx.fetch_add(1) * atoi(e) + (comma ? atoi(comma + 1) : 0)) & 7;
-        }
-        for (int k = 0; k < skew; k++) {
-            hipStream_t ph = nullptr;
-            if (hipStreamCreateWithFlags(&ph, hipStreamNonBlocking) == hipSuccess) c->placeholder_streams.push_back(ph);
-        }
+    // placeholder streams first: they shift the hardware queues -- and so the dispatch pipes -- this context's streams land
+    // on relative to the contexts made before it
+    for (int k = 0; k < (stream_offset & 7); k++) {
+        hipStream_t ph = nullptr;
+        if (hipStreamCreateWithFlags(&ph, hipStreamNonBlocking) == hipSuccess) c->placeholder_streams.push_back(ph);
     }
     bool lanes_ok = true;
     for (int i = 0; i < k16_ctx::N_LANES; i++)
         lanes_ok = lanes_ok && (i > 0 || hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking) == hipSuccess) &&
                    hipEventCreateWithFlags(&c->lanes[i].sort_done, hipEventDisableTiming) == hipSuccess &&
-                   hipEventCreateWithFlags(&c->lanes[i].acc_done, hipEventDisableTiming) == hipSuccess &&
-                   hipEventCreateWithFlags(&c->lanes[i].lvl1_done, hipEventDisableTiming) == hipSuccess &&
-                   hipEventCreateWithFlags(&c->lanes[i].tail_done, hipEventDisableTiming) == hipSuccess;
-    if (const char* e = getenv("K16_SERIALIZE_ACC")) c->serialize_acc = atoi(e) != 0;
-    if (const char* e = getenv("K16_NTT_WG_PER_CU")) c->ntt_wg_per_cu = c->ntt_wg_per_cu_default = (unsigned)std::max(1, std::min(4, atoi(e)));
-    if (const char* e = getenv("K16_WSUM_MLOG_CAP")) c->wsum_mlog_cap = (unsigned)atoi(e);
-    if (const char* e = getenv("K16_GRAPHS")) c->graphs_on = atoi(e) != 0;
-    if (const char* e = getenv("K16_ACC_FENCE")) c->acc_fence_mode = atoi(e);
-    if (const char* e = getenv("K16_ACC_GRID")) c->acc_grid_cap = (unsigned)std::max(0, atoi(e));
-    if (const char* e = getenv("K16_LEAN_SORT")) c->lean_sort = atoi(e) != 0;
-    if (const char* e = getenv("K16_WC_SORT")) c->wc_sort = atoi(e) != 0;
-    if (const char* e = getenv("K16_ACC_DYN")) c->acc_dyn_grid = (unsigned)std::max(0, atoi(e));
-    if (const char* e = getenv("K16_ACC_LDS")) c->acc_lds_bytes = (unsigned)std::min(65536, std::max(0, atoi(e)));
-    if (c->graphs_on && c->acc_fence_mode != 0) {
-        fprintf(stderr, "k16: K16_GRAPHS=1 ignores K16_ACC_FENCE=%d (events of that mode are not recorded on a graph replay)\n",
-                c->acc_fence_mode);
-        c->acc_fence_mode = 0;
-    }
+                   hipEventCreateWithFlags(&c->lanes[i].acc_done, hipEventDisableTiming) == hipSuccess;
     c->stream = c->lanes[0].stream;
     if (!lanes_ok ||
         hipEventCreate(&c->ev_a) != hipSuccess || hipEventCreate(&c->ev_b) != hipSuccess) {
@@ -184,7 +133,7 @@ extern "C" void k16_ctx_destroy(k16_ctx* c)
     (void)hipDeviceSynchronize();
     for (auto& L : c->lanes) {
         k16_devbuf* bufs[] = {&L.ws_counts, &L.ws_offsets, &L.ws_cursor, &L.ws_sorted, &L.ws_segoff, &L.ws_segbucket,
-                              &L.ws_partial, &L.ws_big, &L.ws_misc, &L.ws_lvl_a, &L.ws_lvl_b, &L.ws_lvl_c,
+                              &L.ws_partial, &L.ws_big, &L.ws_lvl_a, &L.ws_lvl_b, &L.ws_lvl_c,
                               &L.ws_lvl_d, &L.ws_scan, &L.ws_conv, &L.ws_narrow};
         for (auto* b : bufs)
             if (b->p) (void)hipFree(b->p);
@@ -207,8 +156,6 @@ extern "C" void k16_ctx_destroy(k16_ctx* c)
             if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
         if (L.sort_done) (void)hipEventDestroy(L.sort_done);
         if (L.acc_done) (void)hipEventDestroy(L.acc_done);
-        if (L.lvl1_done) (void)hipEventDestroy(L.lvl1_done);
-        if (L.tail_done) (void)hipEventDestroy(L.tail_done);
         if (L.stream && (&L == &c->lanes[0] || L.stream != c->lanes[0].stream)) (void)hipStreamDestroy(L.stream);
     }
     delete c;
@@ -285,28 +232,19 @@ extern "C" int k16_ctx_set_option(k16_ctx* c, int option, int value)
     if (!c) return K16_ERR_ARG;
     switch (option) {
     case K16_OPT_GRAPHS:
-        // the K16_ACC_FENCE experiments record their events between the launches of a tail; a replayed graph does not
-        // (nothing on the host runs then), so the ordering those modes promise would silently be lost
-        if (value && c->acc_fence_mode != 0) {
-            c->err = "K16_OPT_GRAPHS cannot be combined with K16_ACC_FENCE != 0";
-            return K16_ERR_ARG;
-        }
         c->graphs_on = value != 0;
         return K16_OK;
     case K16_OPT_PIPELINED_MSM:
         // several MSMs in flight on different lanes, throughput over latency
         c->serialize_acc = value != 0;
         c->wsum_mlog_cap = value ? 4 : 3;
-        // (the lean sort -- every sort kernel in <= 32 VGPRs, resident beside another lane's accumulation -- is NOT switched
-        // on here: measured, it moves the sort under the accumulation but the step does not get shorter, the chip being
-        // power-limited during a pipelined run (profiles/r03/lean_sort_and_power.md); K16_LEAN_SORT=1 selects it)
         return K16_OK;
     case K16_OPT_SHARED_GPU:
         // several provers (contexts) prove on this GPU at once: proofs per second over the latency of one.  The NTT passes
         // then keep three workgroups per CU instead of four, which leaves a SIMD the registers for a wave of another
         // prover's bucket accumulation: +2.5-3 % proofs/s with two provers, +0-0.3 ms on a proof alone
         // (profiles/r04/ab_ntt_wg_per_cu.log)
-        c->ntt_wg_per_cu = value ? std::min(3u, c->ntt_wg_per_cu_default) : c->ntt_wg_per_cu_default;
+        c->ntt_wg_per_cu = value ? 3u : 4u;
         return K16_OK;
     case K16_OPT_YIELDING_WAITS:
         c->yielding_waits = value != 0;

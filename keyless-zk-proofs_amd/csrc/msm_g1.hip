@@ -26,15 +26,8 @@ int k16_msm_enqueue_g1(k16_ctx* ctx, const void* d_bases, const void* d_scalars,
         rows = (const k16::G1Aff*)L.ws_conv.p;
         // the conversion rides in the sort's counting pass when there is one (LDS partition sort, no reused sort, no
         // captured graphs -- a graph would pin this call's table pointer); otherwise it is a kernel of its own
-        const bool fuse = n <= (1u << 24) && !ctx->reuse_sort && ctx->derive_lane < 0 && !ctx->graphs_on && !ctx->tune.atomic_sort &&
-                          !ctx->tune.no_fused_convert;
-        if (ctx->lean_sort) {
-            // lean sort: the counting pass stays at 25 VGPRs (the fused conversion made it 82), and the conversion is the
-            // 5-doubling kernel -- both fit beside another lane's bucket accumulation
-            hipLaunchKernelGGL(k_convert_bases_lean, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0,
-                               k16_lane_stream(ctx, ctx->cur_lane), (const uint4*)d_bases, (uint4*)L.ws_conv.p, 2 * n);
-            K16_HIP(ctx, hipGetLastError());
-        } else if (fuse)
+        const bool fuse = n <= (1u << 24) && !ctx->reuse_sort && ctx->derive_lane < 0 && !ctx->graphs_on && !ctx->tune.atomic_sort;
+        if (fuse)
             conv_in = d_bases;
         else if ((rc = k16_msm_prepare_g1(ctx, d_bases, n, L.ws_conv.p, k16_lane_stream(ctx, ctx->cur_lane))))
             return rc;

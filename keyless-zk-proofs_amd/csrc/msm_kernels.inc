@@ -217,9 +217,6 @@ struct PartCfg {
     static constexpr unsigned SHIFT = 24;                   // 24-bit point index, 7 low bucket bits, sign
     static constexpr bool     FLAT  = false;
     static constexpr unsigned TILE  = PART_TILE;
-    // write-combining scatter pass (k_part_wc): points per 1024-thread workgroup, staging rounds (bin ranges) per tile
-    static constexpr unsigned WC_TILE   = 4096;
-    static constexpr unsigned WC_ROUNDS = 8;
 };
 // Fixed-base MSM over precomputed window tables (row w*n + i = 2^(C*w) * P_i): ONE bucket set for all digit positions,
 // so the bucket is the magnitude alone and the entry carries the table row (25 bits: n * W < 2^25), 6 low bucket bits.
@@ -238,8 +235,6 @@ struct PartCfgFlat {
     // 2^21-point H MSM.  A 4096-point tile halves them and doubles the run length; measured: 378 vs 397 us for the
     // scatter pass, no gain -- the pass is bound by its two workgroups per CU, not by the reservations.)
     static constexpr unsigned TILE  = PART_TILE;
-    static constexpr unsigned WC_TILE   = 8192;
-    static constexpr unsigned WC_ROUNDS = 16;
 };
 
 // Exclusive scan of the <= 8192 bin counts of the partition into LDS, by one 256-thread workgroup (thread t owns `per`
@@ -288,14 +283,6 @@ __device__ __forceinline__ void part_scan_lds(const uint32_t* __restrict__ gcoun
 // tiles before it -- in atomic order -- took), the latter from a zero-based global cursor.  Workgroup 0 also writes the
 // bin starts and the slice table pass 3 needs.
 //
-// X8 (round 4, K16_X8=1; measured WITHOUT effect and off by default -- WRITE_SIZE 1.15 GB either way, the single-workgroup
-// k_bin_starts8 costs 70-90 us -- kept as the record of the experiment): every bin's region is cut into EIGHT sub-regions, one per group of workgroups that share an XCD (tile % 8:
-// blocks are dealt round-robin over the XCDs, MI355X_MICROARCH.md "Workgroup dispatch"; a label for speed, never relied on
-// for correctness), with their own counters and cursors g[x * NB1 + b].  A (tile, bin) run is 13-128 bytes; with one cursor
-// per bin consecutive runs of a bin come from tiles on different XCDs, every 128-byte line of the output is assembled from
-// the partial write-backs of up to eight L2s, and the pass wrote 6-9x its bytes (rocprofv3 WRITE_SIZE, profiles/r03).  With
-// a cursor per (XCD group, bin) a line is filled by tiles that share an L2 and leaves it once.  The starts of the 8 * NB1
-// sub-regions come from k_bin_starts8 (bin-major order, so a bin is still one contiguous range for pass 3).
 // HS (counting pass of the prover's H MSM): the scalars do not exist yet -- scalar i is fromMontgomery(a[i] * b[i] - c[i])
 // (groth16.cpp:266-275) of the three coset evaluations (packed R' values of Fr), formed here, written to `scalars` for the
 // later passes and counted in the same breath: the kernel that used to produce them wrote 64 MB for this pass to read back,
@@ -321,7 +308,7 @@ __global__ void __launch_bounds__(256) k_hs_fill(uint4* __restrict__ scalars, ui
     scalars[2 * i + 1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
 }
 
-template <class P, bool SCATTER, bool CONV = false, bool X8 = false, bool HS = false>
+template <class P, bool SCATTER, bool CONV = false, bool HS = false>
 __global__ void __launch_bounds__(256) k_part(const uint4* __restrict__ scalars, uint64_t n, uint32_t* __restrict__ g,
                                               uint32_t* __restrict__ part, const k16::Aff<k16::Fq>* __restrict__ conv_in,
                                               k16::Aff<k16::Fq>* __restrict__ conv_out, const uint32_t* __restrict__ gcount,
@@ -330,7 +317,7 @@ __global__ void __launch_bounds__(256) k_part(const uint4* __restrict__ scalars,
                                               const k16::Fr* __restrict__ hs_a = nullptr, const k16::Fr* __restrict__ hs_b = nullptr,
                                               const k16::Fr* __restrict__ hs_c = nullptr)
 {
-    static_assert(!HS || (!SCATTER && !CONV && !X8), "the H scalars are formed by the plain counting pass");
+    static_assert(!HS || (!SCATTER && !CONV), "the H scalars are formed by the plain counting pass");
     // skip: bit i set = point i is left out of the sort (its table row is (0,0): k16_msm_zero_row_mask) -- both passes
     k16_short_kernel_prio();
     extern __shared__ uint32_t  part_lds[];
@@ -356,12 +343,7 @@ __global__ void __launch_bounds__(256) k_part(const uint4* __restrict__ scalars,
         else
             for_signed_digits<P::C>(k, f);
     };
-    if (SCATTER && X8) { // gcount = the sub-region starts of k_bin_starts8, [x][bin]
-        const uint32_t* __restrict__ st8 = gcount + (size_t)(blockIdx.x & 7u) * P::NB1;
-        for (unsigned b = threadIdx.x; b < P::NB1; b += blockDim.x) base[b] = st8[b];
-        k16_lds_sync();
-    }
-    if (SCATTER && !X8) {
+    if (SCATTER) {
         if (blockIdx.x == 0) { // the tables of pass 3 (slices first: `base` is reused for the starts)
             part_scan_lds<true>(gcount, P::NB1, base, sh, &s_total);
             for (unsigned b = threadIdx.x; b < P::NB1; b += blockDim.x) gslice[b] = base[b];
@@ -406,12 +388,12 @@ __global__ void __launch_bounds__(256) k_part(const uint4* __restrict__ scalars,
         for (unsigned j = 0; j < BPT; j++) {
             const unsigned b = threadIdx.x + j * 256;
             uint32_t       h = b < P::NB1 ? hget(b) : 0u;
-            got[j]           = h ? atomicAdd(&g[(X8 ? (tile & 7u) * P::NB1 : 0u) + b], h) : 0u;
+            got[j]           = h ? atomicAdd(&g[b], h) : 0u;
         }
 #pragma unroll
         for (unsigned j = 0; j < BPT; j++) {
             const unsigned b = threadIdx.x + j * 256;
-            if (b < P::NB1) base[b] += got[j]; // start of the bin (of its sub-region) + what earlier tiles reserved
+            if (b < P::NB1) base[b] += got[j]; // start of the bin + what earlier tiles reserved
         }
         k16_lds_sync();
         for (unsigned b = threadIdx.x; b < HW; b += blockDim.x) hist[b] = 0;
@@ -462,91 +444,15 @@ __global__ void __launch_bounds__(256) k_part(const uint4* __restrict__ scalars,
         k16_lds_sync();
         for (unsigned b = threadIdx.x; b < P::NB1; b += blockDim.x) {
             uint32_t h = hget(b);
-            if (h) atomicAdd(&g[(X8 ? (tile & 7u) * P::NB1 : 0u) + b], h);
+            if (h) atomicAdd(&g[b], h);
         }
         k16_lds_sync();
     }
 }
 
-// Starts of the 8 * NB1 sub-regions of the partition (X8, see k_part): exclusive scan of gcount8[x][bin] in bin-major order
-// into gstart8[x][bin]; per bin the start and the slice table pass 3 needs.  One workgroup.
-__global__ void __launch_bounds__(1024) k_bin_starts8(const uint32_t* __restrict__ gcount8, uint32_t nb1,
-                                                      uint32_t* __restrict__ gstart8, uint32_t* __restrict__ gstart,
-                                                      uint32_t* __restrict__ gslice)
-{
-    k16_short_kernel_prio();
-    __shared__ uint32_t sa[1024], sb[1024];
-    const unsigned per = (nb1 + 1023) / 1024;
-    uint32_t       a = 0, b = 0;
-    for (unsigned j = 0; j < per; j++) {
-        const unsigned i = threadIdx.x * per + j;
-        if (i < nb1) {
-            uint32_t v = 0;
-#pragma unroll
-            for (unsigned x = 0; x < 8; x++) v += gcount8[x * nb1 + i];
-            a += v;
-            b += (v + PART_SLICE - 1) / PART_SLICE;
-        }
-    }
-    sa[threadIdx.x] = a;
-    sb[threadIdx.x] = b;
-    k16_lds_sync();
-    for (unsigned o = 1; o < 1024; o <<= 1) {
-        const uint32_t ta = threadIdx.x >= o ? sa[threadIdx.x - o] : 0u, tb = threadIdx.x >= o ? sb[threadIdx.x - o] : 0u;
-        k16_lds_sync();
-        sa[threadIdx.x] += ta;
-        sb[threadIdx.x] += tb;
-        k16_lds_sync();
-    }
-    uint32_t ra = sa[threadIdx.x] - a, rb = sb[threadIdx.x] - b;
-    for (unsigned j = 0; j < per; j++) {
-        const unsigned i = threadIdx.x * per + j;
-        if (i < nb1) {
-            gstart[i] = ra;
-            gslice[i] = rb;
-            uint32_t v = 0;
-#pragma unroll
-            for (unsigned x = 0; x < 8; x++) {
-                const uint32_t cx = gcount8[x * nb1 + i];
-                gstart8[x * nb1 + i] = ra + v;
-                v += cx;
-            }
-            ra += v;
-            rb += (v + PART_SLICE - 1) / PART_SLICE;
-        }
-    }
-    if (threadIdx.x == 1023) {
-        gstart[nb1] = sa[1023];
-        gslice[nb1] = sb[1023];
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Write-combining scatter pass (round 3).  rocprofv3 --pmc WRITE_SIZE showed the SCATTER pass of k_part writing 400-470 MB
-// to the memory side for 67 MB of entries (1.0 GB for 109 MB in the fixed-base H sort): a (tile, bin) run is 3-8 entries
-// stored by unrelated lanes at unrelated times, every 4-byte store ends as its own 32-byte sector write, and the L2 does
-// not merge them whatever the run length (PART_TILE 2048 / 4096 / 8192: 472 / 445 / 387 MB).  Here a 1024-thread workgroup
-// owns a LARGE tile (4096 / 8192 points: runs of 13-16 entries), and the entries leave through LDS in bin-major order:
-//   1  histogram of the tile over all bins (LDS atomics)                 -> cur[bin] = count
-//   2  exclusive scan -> tile_off; one global reservation per non-empty bin; cur[bin] = tile_off, gdl[bin] = global
-//      position of the tile's run minus tile_off
-//   3  R rounds over bin ranges: the lanes walk their digits again, entries of the round's bins take their rank
-//      (atomicAdd on cur) and are written to stage[rank position - round base] with their bin; then the round's stretch of
-//      the tile-sorted order is copied out by consecutive lanes: part[gdl[bin] + position] -- adjacent lanes, adjacent
-//      addresses, so a run is written by one or two store transactions.
-// A tile whose busiest round does not fit the staging buffer (skewed scalars) stores directly, like k_part: correct for
-// every input, fast for the uniform ones (the H MSM's scalars, the MSM benchmark).
 constexpr unsigned WC_THREADS = 1024;
-template <class P>
-struct WcGeom {
-    static constexpr unsigned ENTRIES = P::WC_TILE * (P::FLAT ? P::W : P::W);            // an upper bound per tile
-    static constexpr unsigned CAP     = ((ENTRIES / P::WC_ROUNDS) * 3 / 2 + 63) & ~63u;  // staging entries per round
-    static constexpr unsigned BPR     = (P::NB1 + P::WC_ROUNDS - 1) / P::WC_ROUNDS;      // bins per round
-    // LDS words: cur[NB1 + 1] | gdl[NB1] | stage[CAP] | sbin[CAP / 2] | scan scratch [1024] | flags
-    static constexpr unsigned LDS_WORDS = (P::NB1 + 1) + P::NB1 + CAP + CAP / 2 + WC_THREADS + 8;
-};
-// exclusive starts of the partition's bins (and of their slices for pass 3): one workgroup, between the counting and the
-// scatter pass (k_part's scatter pass had every workgroup redo this scan; with 8192 bins that was 25 us of its 375)
+// exclusive starts of the partition's bins (and of their slices for pass 3): one workgroup, between the counting pass and
+// the staged scatter pass (k_part_stage)
 __global__ void __launch_bounds__(WC_THREADS) k_bin_starts(const uint32_t* __restrict__ gcount, uint32_t nb1,
                                                           uint32_t* __restrict__ gstart, uint32_t* __restrict__ gslice)
 {
@@ -587,135 +493,12 @@ __global__ void __launch_bounds__(WC_THREADS) k_bin_starts(const uint32_t* __res
     }
 }
 
-template <class P>
-__global__ void __launch_bounds__(WC_THREADS) k_part_wc(const uint4* __restrict__ scalars, uint64_t n, uint32_t* __restrict__ g,
-                                                        uint32_t* __restrict__ part, const uint32_t* __restrict__ gstart)
-{
-    k16_short_kernel_prio();
-    typedef WcGeom<P>          G;
-    extern __shared__ uint32_t wc_lds[];
-    uint32_t* cur   = wc_lds;                  // [NB1 + 1]
-    uint32_t* gdl   = cur + P::NB1 + 1;        // [NB1]
-    uint32_t* stage = gdl + P::NB1;            // [CAP]
-    uint16_t* sbin  = reinterpret_cast<uint16_t*>(stage + G::CAP); // [CAP]
-    uint32_t* sh    = stage + G::CAP + G::CAP / 2; // [1024]
-    uint32_t* flags = sh + WC_THREADS;             // [0] direct mode
-    constexpr unsigned PPT = P::WC_TILE / WC_THREADS;
-    constexpr unsigned BPT = (P::NB1 + WC_THREADS - 1) / WC_THREADS;
-    auto bin_of = [](unsigned w, uint32_t m1) -> uint32_t { return P::FLAT ? (m1 >> P::LO) : ((w << P::HI) + (m1 >> P::LO)); };
-    auto digits = [](const uint32_t (&k)[8], auto f) {
-        if constexpr (P::FLAT)
-            for_signed_digits_flat<P::C>(k, f);
-        else
-            for_signed_digits<P::C>(k, f);
-    };
-    const uint32_t tile = blockIdx.x;
-    // the tile's scalars stay in registers for all rounds
-    uint4 sc[PPT][2];
-#pragma unroll
-    for (unsigned p = 0; p < PPT; p++) {
-        const uint64_t i = (uint64_t)tile * P::WC_TILE + p * WC_THREADS + threadIdx.x;
-        if (i < n) {
-            sc[p][0] = scalars[2 * i];
-            sc[p][1] = scalars[2 * i + 1];
-        } else {
-            sc[p][0] = sc[p][1] = make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
-    for (unsigned b = threadIdx.x; b <= P::NB1; b += WC_THREADS) cur[b] = 0;
-    if (threadIdx.x == 0) flags[0] = 0;
-    k16_lds_sync();
-    // 1: histogram
-#pragma unroll
-    for (unsigned p = 0; p < PPT; p++) {
-        uint32_t k[8] = {sc[p][0].x, sc[p][0].y, sc[p][0].z, sc[p][0].w, sc[p][1].x, sc[p][1].y, sc[p][1].z, sc[p][1].w};
-        digits(k, [&](unsigned w, uint32_t m1, uint32_t) { atomicAdd(&cur[bin_of(w, m1)], 1u); });
-    }
-    k16_lds_sync();
-    // 2: exclusive scan of cur[0 .. NB1) in place (thread t owns BPT consecutive bins), reservations, gdl
-    {
-        uint32_t h[BPT], sum = 0;
-#pragma unroll
-        for (unsigned j = 0; j < BPT; j++) {
-            const unsigned b = threadIdx.x * BPT + j;
-            h[j]             = b < P::NB1 ? cur[b] : 0u;
-            sum += h[j];
-        }
-        sh[threadIdx.x] = sum;
-        k16_lds_sync();
-        for (unsigned o = 1; o < WC_THREADS; o <<= 1) {
-            const uint32_t t = threadIdx.x >= o ? sh[threadIdx.x - o] : 0u;
-            k16_lds_sync();
-            sh[threadIdx.x] += t;
-            k16_lds_sync();
-        }
-        uint32_t run = sh[threadIdx.x] - sum;
-        uint32_t got[BPT];
-#pragma unroll
-        for (unsigned j = 0; j < BPT; j++) {
-            const unsigned b = threadIdx.x * BPT + j;
-            got[j]           = (b < P::NB1 && h[j]) ? atomicAdd(&g[b], h[j]) : 0u;
-        }
-#pragma unroll
-        for (unsigned j = 0; j < BPT; j++) {
-            const unsigned b = threadIdx.x * BPT + j;
-            if (b < P::NB1) {
-                cur[b] = run;
-                gdl[b] = gstart[b] + got[j] - run;
-                run += h[j];
-            }
-        }
-        if (threadIdx.x == WC_THREADS - 1) cur[P::NB1] = sh[WC_THREADS - 1];
-    }
-    k16_lds_sync();
-    // does every round fit the staging buffer?  (round r: bins [r * BPR, (r + 1) * BPR))
-    if (threadIdx.x < P::WC_ROUNDS) {
-        const unsigned lo = threadIdx.x * G::BPR, hi = min(lo + G::BPR, P::NB1);
-        if (lo < P::NB1 && cur[hi] - cur[lo] > G::CAP) atomicOr(&flags[0], 1u);
-    }
-    k16_lds_sync();
-    const bool direct = flags[0] != 0;
-    // 3: rounds
-#pragma clang loop unroll(disable)
-    for (unsigned r = 0; r < P::WC_ROUNDS; r++) {
-        const unsigned lo = r * G::BPR, hi = min(lo + G::BPR, P::NB1);
-        if (lo >= P::NB1) break;
-        const uint32_t base = cur[lo]; // pristine: no entry of this round has been ranked yet
-        const uint32_t cnt  = (hi < P::NB1 ? cur[hi] : cur[P::NB1]) - base;
-        k16_lds_sync(); // everybody has read base / cnt before cur[lo ..] starts moving
-#pragma unroll
-        for (unsigned p = 0; p < PPT; p++) {
-            const uint64_t i = (uint64_t)tile * P::WC_TILE + p * WC_THREADS + threadIdx.x;
-            uint32_t k[8] = {sc[p][0].x, sc[p][0].y, sc[p][0].z, sc[p][0].w, sc[p][1].x, sc[p][1].y, sc[p][1].z, sc[p][1].w};
-            digits(k, [&](unsigned w, uint32_t m1, uint32_t neg) {
-                const uint32_t b = bin_of(w, m1);
-                if (b >= lo && b < hi) {
-                    const uint32_t pos = atomicAdd(&cur[b], 1u);
-                    const uint32_t row = P::FLAT ? (uint32_t)(w * n + i) : (uint32_t)i;
-                    const uint32_t e   = (neg << 31) | ((m1 & ((1u << P::LO) - 1u)) << P::SHIFT) | row;
-                    if (direct) {
-                        part[gdl[b] + pos] = e;
-                    } else {
-                        stage[pos - base] = e;
-                        sbin[pos - base]  = (uint16_t)b;
-                    }
-                }
-            });
-        }
-        k16_lds_sync();
-        if (!direct) {
-            for (uint32_t j = threadIdx.x; j < cnt; j += WC_THREADS) part[gdl[sbin[j]] + base + j] = stage[j];
-        }
-        // (the next round's first barrier orders these reads of stage / sbin before its writes)
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // Staged scatter pass with FIVE-byte entries (round 4).  What the measurements of rounds 3-4 say about this pass: the
 // memory side merges 4-byte stores only when they arrive close together -- the bucket pass, whose workgroups each fill a
 // 13 KB region within microseconds, writes 1.04x its bytes, the scatter pass of k_part, whose (tile, bin) runs of 3-32
 // entries are completed by other tiles much later, 6-9x (398-472 MB for 67 MB at 2^20 x c16, 1.0-1.15 GB for 109 MB in the H
-// sort), and neither longer runs (PART_TILE 2048 ... 8192) nor per-XCD sub-regions of every bin (K16_X8: lines assembled in
+// sort), and neither longer runs (PART_TILE 2048 ... 8192) nor per-XCD sub-regions of every bin (lines assembled in
 // ONE L2) change that.  So a workgroup has to write whole sectors itself: the tile's entries are ranked into LDS in
 // bin-major order and copied out by half-waves, one run at a time, adjacent lanes to adjacent addresses.  That only pays
 // when a run is long, i.e. with FEW bins -- and a 32-bit entry (sign + low key bits + 25-bit row) forces 2^13 of them for
@@ -734,7 +517,6 @@ struct PartCfgFlat5 {
     static constexpr unsigned SHIFT = 25;
     static constexpr bool     FLAT  = true;
     static constexpr unsigned TILE  = PART_TILE;            // the counting pass (k_part<P, false>)
-    static constexpr unsigned WC_TILE = 8192, WC_ROUNDS = 16; // (unused: k_part_wc is not instantiated for it)
 #ifndef K16_ST_TILE_FLAT
 #define K16_ST_TILE_FLAT 2048
 #endif
@@ -753,7 +535,6 @@ struct PartCfg5 {
     static constexpr unsigned SHIFT = 24;
     static constexpr bool     FLAT  = false;
     static constexpr unsigned TILE  = PART_TILE;
-    static constexpr unsigned WC_TILE = 4096, WC_ROUNDS = 8;
     static constexpr unsigned ST_TILE = 1024;               // (2048 points x 17 windows x 5 bytes do not fit the LDS)
 };
 constexpr unsigned ST_THREADS = 1024;
@@ -867,155 +648,16 @@ __global__ void __launch_bounds__(ST_THREADS) k_part_stage(const uint4* __restri
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// "Lean sort": every kernel of the bucket sort in at most 32 VGPRs.  A bucket accumulation (159 VGPRs, three waves per
-// SIMD = 480 of the 512 registers of a SIMD lane) leaves exactly 32 registers per lane free, so a workgroup of another
-// lane's sort can only become resident beside it if its waves need no more than that -- otherwise it waits until the
-// accumulation's 7000 workgroups have drained (kernel traces: the 82-register counting pass took 494 us beside an
-// accumulation, its 25-register variant 47 us; profiles/r03).  With the lean kernels the sort of MSM k+1 runs UNDER the
-// accumulation of MSM k instead of in the gap behind it.  They trade instruction-level parallelism (one scalar per lane
-// in flight instead of eight, no 17 reservations at once) for that: slower alone, hidden when pipelined
-// (k16_ctx::lean_sort; the prover's single MSMs keep the fat kernels).
-//
-// k_part_scatter_lean: the SCATTER pass of k_part (same LDS layout, same outputs), one point per lane at a time.
-template <class P>
-__global__ void __launch_bounds__(256) k_part_scatter_lean(const uint4* __restrict__ scalars, uint64_t n, uint32_t* __restrict__ g,
-                                                           uint32_t* __restrict__ part, const uint32_t* __restrict__ gcount,
-                                                           uint32_t* __restrict__ gstart, uint32_t* __restrict__ gslice)
-{
-    k16_short_kernel_prio();
-    extern __shared__ uint32_t part_lds[];
-    __shared__ uint32_t         sh[256];
-    __shared__ uint32_t         s_total;
-    constexpr unsigned          HW = (P::NB1 + 1) / 2;
-    uint32_t*                   hist = part_lds;
-    uint32_t*                   base = part_lds + HW;
-    auto hadd = [&](uint32_t b) -> uint32_t {
-        const unsigned sh16 = (b & 1u) << 4;
-        return (atomicAdd(&hist[b >> 1], 1u << sh16) >> sh16) & 0xffffu;
-    };
-    auto hget = [&](uint32_t b) -> uint32_t { return (hist[b >> 1] >> ((b & 1u) << 4)) & 0xffffu; };
-    auto bin_of = [](unsigned w, uint32_t m1) -> uint32_t { return P::FLAT ? (m1 >> P::LO) : ((w << P::HI) + (m1 >> P::LO)); };
-    auto digits = [](const uint32_t (&k)[8], auto f) {
-        if constexpr (P::FLAT)
-            for_signed_digits_flat<P::C>(k, f);
-        else
-            for_signed_digits<P::C>(k, f);
-    };
-    if (blockIdx.x == 0) {
-        part_scan_lds<true>(gcount, P::NB1, base, sh, &s_total);
-        for (unsigned b = threadIdx.x; b < P::NB1; b += blockDim.x) gslice[b] = base[b];
-        if (threadIdx.x == 0) gslice[P::NB1] = s_total;
-        k16_lds_sync();
-    }
-    part_scan_lds<false>(gcount, P::NB1, base, sh, &s_total);
-    if (blockIdx.x == 0) {
-        for (unsigned b = threadIdx.x; b < P::NB1; b += blockDim.x) gstart[b] = base[b];
-        if (threadIdx.x == 0) gstart[P::NB1] = s_total;
-    }
-    constexpr unsigned PPT  = P::TILE / 256;
-    constexpr unsigned BPT  = (P::NB1 + 255) / 256;
-    const uint32_t     tile = blockIdx.x;
-    for (unsigned b = threadIdx.x; b < HW; b += blockDim.x) hist[b] = 0;
-    k16_lds_sync();
-#pragma clang loop unroll(disable)
-    for (unsigned p = 0; p < PPT; p++) {
-        const uint64_t i = (uint64_t)tile * P::TILE + p * 256 + threadIdx.x;
-        if (i < n) {
-            const uint4 lo = scalars[2 * i], hi = scalars[2 * i + 1];
-            uint32_t    k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            digits(k, [&](unsigned w, uint32_t m1, uint32_t) { (void)hadd(bin_of(w, m1)); });
-        }
-    }
-    k16_lds_sync();
-    // reservations: four of a lane's bins in flight at a time (the fat kernel issues all BPT at once)
-#pragma clang loop unroll(disable)
-    for (unsigned j0 = 0; j0 < BPT; j0 += 4) {
-        uint32_t got[4];
-#pragma unroll
-        for (unsigned jj = 0; jj < 4; jj++) {
-            const unsigned b = threadIdx.x + (j0 + jj) * 256;
-            const uint32_t h = b < P::NB1 ? hget(b) : 0u;
-            got[jj]          = h ? atomicAdd(&g[b], h) : 0u;
-        }
-#pragma unroll
-        for (unsigned jj = 0; jj < 4; jj++) {
-            const unsigned b = threadIdx.x + (j0 + jj) * 256;
-            if (b < P::NB1) base[b] += got[jj];
-        }
-    }
-    k16_lds_sync();
-    for (unsigned b = threadIdx.x; b < HW; b += blockDim.x) hist[b] = 0;
-    k16_lds_sync();
-#pragma clang loop unroll(disable)
-    for (unsigned p = 0; p < PPT; p++) {
-        const uint64_t i = (uint64_t)tile * P::TILE + p * 256 + threadIdx.x;
-        if (i < n) {
-            const uint4 lo = scalars[2 * i], hi = scalars[2 * i + 1]; // second read of the tile's 64 KB: L2
-            uint32_t    k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            digits(k, [&](unsigned w, uint32_t m1, uint32_t neg) {
-                const uint32_t b   = bin_of(w, m1);
-                const uint32_t r   = hadd(b);
-                const uint32_t row = P::FLAT ? (uint32_t)(w * n + i) : (uint32_t)i;
-                part[base[b] + r] = (neg << 31) | ((m1 & ((1u << P::LO) - 1u)) << P::SHIFT) | row;
-            });
-        }
-    }
-}
-
-// canonical zkey-format G1 table -> packed R'-domain rows, one COORDINATE per lane and without the 9-limb multiply of
-// k_convert_bases: x * R' = (x * R) * 2^5 mod p is five modular doublings of the canonical value (x * R < p), each a
-// shift and a conditional subtraction of p on eight 32-bit limbs.  The row is the canonical representative (< p <= the
-// rows' bound 2p); (0,0) stays (0,0).
-__global__ void __launch_bounds__(256) k_convert_bases_lean(const uint4* __restrict__ in, uint4* __restrict__ out, uint64_t ncoord)
-{
-    k16_short_kernel_prio();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ncoord) return;
-    const uint4 a = in[2 * i], b = in[2 * i + 1];
-    uint32_t    v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma clang loop unroll(disable)
-    for (int d = 0; d < 5; d++) {
-        // v < p < 2^254: 2v < 2^255 fits
-#pragma unroll
-        for (int k = 7; k > 0; k--) v[k] = (v[k] << 1) | (v[k - 1] >> 31);
-        v[0] <<= 1;
-        // 2v >= p ?  (compared from the top limb; no 8-limb difference is kept: this kernel must stay within 32 VGPRs)
-        bool ge = true;
-#pragma unroll
-        for (int k = 7; k >= 0; k--) {
-            if (v[k] != FqParams::P[k]) {
-                ge = v[k] > FqParams::P[k];
-                break;
-            }
-        }
-        if (ge) {
-            unsigned borrow = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = __builtin_subc(v[k], FqParams::P[k], borrow, &borrow);
-        }
-    }
-    out[2 * i]     = make_uint4(v[0], v[1], v[2], v[3]);
-    out[2 * i + 1] = make_uint4(v[4], v[5], v[6], v[7]);
-}
-
 // pass 3, one workgroup per (bin, slice of <= PART_SLICE entries).
 //   MODE 0 (count)    LDS histogram over the low digit bits -> global bucket counts
 //   MODE 1 (scatter)  reserve each bucket's run with one global atomic per non-empty bucket per slice, rank the entries
 //                     in LDS, write the final point-index lists
-//   MODE 2 (fused)    a bin that fits ONE slice (every bin of a uniform MSM: n*W / NB1 ~ 4096 entries) is finished in
-//                     this launch: its workgroup sees all of the bin's entries, so the bucket counts are its LDS
-//                     histogram and a bucket's offset is  bin start + local prefix  -- no global scan, no global atomics,
-//                     no second pass over the entries.  Bins with more slices (skewed inputs) are only counted here
-//                     and scattered by a MODE 1 launch after the global scan, which skips the single-slice bins.
 // Lanes that share the first active lane's key are ranked by ballot (skewed inputs put most of a bin into one bucket).
-// LEAN: the slice's entries are not kept in registers between the two loops (32 VGPRs less; each loop reads them from
-// L2) -- see "lean sort" below.
-template <class P, int MODE, bool LEAN = false>
+template <class P, int MODE>
 __global__ void __launch_bounds__(256) k_part_bins(const uint32_t* __restrict__ gstart, const uint32_t* __restrict__ gslice,
                                                    uint32_t nb1, const uint32_t* __restrict__ part,
                                                    uint32_t* __restrict__ counts_or_cursor, uint32_t* __restrict__ sorted,
-                                                   uint32_t skip_single, const uint32_t* __restrict__ remap,
+                                                   const uint32_t* __restrict__ remap,
                                                    const uint8_t* __restrict__ side = nullptr, uint32_t small_cap = 0,
                                                    const uint64_t* __restrict__ drop = nullptr)
 {
@@ -1026,7 +668,6 @@ __global__ void __launch_bounds__(256) k_part_bins(const uint32_t* __restrict__ 
     constexpr unsigned  HN  = LON > 256 ? LON : 256;   // five-byte entries (PartCfg*5): 512 low keys, the upper bits in `side`
     constexpr bool      SIDE = LON > 128;
     constexpr unsigned  LO4  = P::LO4; // key bits inside the 32-bit entry
-    static_assert(!SIDE || (MODE != 2 && !LEAN), "five-byte entries: count + scatter passes only");
     __shared__ uint32_t h[HN], base[HN];
     __shared__ uint32_t s_bin;
     const uint32_t      g = blockIdx.x;
@@ -1046,60 +687,50 @@ __global__ void __launch_bounds__(256) k_part_bins(const uint32_t* __restrict__ 
     for (unsigned t = threadIdx.x; t < HN; t += 256) h[t] = 0;
     k16_lds_sync();
     const uint32_t bin    = s_bin;
-    const bool     single = gslice[bin + 1] - gslice[bin] == 1;
-    if (MODE == 1 && skip_single && single) return; // finished by the fused launch
     if (small_cap && gstart[bin + 1] - gstart[bin] <= small_cap) return; // finished by k_bins_stage
     const uint32_t s0  = gstart[bin] + (g - gslice[bin]) * PART_SLICE;
     const uint32_t s1  = min(s0 + PART_SLICE, gstart[bin + 1]);
     // the slice's entries (<= 32 per lane) are loaded once, all loads in flight together, and serve both passes: the
     // two loops used to pay one dependent global-load latency per 256 entries each (16 + 16 round trips for a 4096-entry bin)
     constexpr unsigned EPT = PART_SLICE / 256;
-    uint32_t           ent[LEAN ? 1 : EPT];
+    uint32_t           ent[EPT];
     uint32_t           sdp[SIDE ? EPT / 4 : 1]; // side bytes, four to a register
     uint32_t           dropped = 0;             // bit k: entry k of this lane is left out
     static_assert(EPT <= 32, "one bit per entry of a lane");
-    if constexpr (!LEAN) {
+#pragma unroll
+    for (unsigned k = 0; k < EPT; k++) {
+        const uint32_t j = s0 + k * 256 + threadIdx.x;
+        ent[k]           = j < s1 ? part[j] : 0xffffffffu;
+    }
+    if (drop) {
+#pragma unroll
+        for (unsigned k = 0; k < EPT; k++) {
+            const uint32_t j  = s0 + k * 256 + threadIdx.x;
+            const uint32_t pt = ent[k] & ((1u << P::SHIFT) - 1u);
+            if (j < s1 && ((drop[pt >> 6] >> (pt & 63u)) & 1ull)) dropped |= 1u << k;
+        }
+    }
+    if constexpr (SIDE) {
+#pragma unroll
+        for (unsigned k = 0; k < EPT / 4; k++) sdp[k] = 0;
 #pragma unroll
         for (unsigned k = 0; k < EPT; k++) {
             const uint32_t j = s0 + k * 256 + threadIdx.x;
-            ent[k]           = j < s1 ? part[j] : 0xffffffffu;
-        }
-        if (drop) {
-#pragma unroll
-            for (unsigned k = 0; k < EPT; k++) {
-                const uint32_t j  = s0 + k * 256 + threadIdx.x;
-                const uint32_t pt = ent[k] & ((1u << P::SHIFT) - 1u);
-                if (j < s1 && ((drop[pt >> 6] >> (pt & 63u)) & 1ull)) dropped |= 1u << k;
-            }
-        }
-        if constexpr (SIDE) {
-#pragma unroll
-            for (unsigned k = 0; k < EPT / 4; k++) sdp[k] = 0;
-#pragma unroll
-            for (unsigned k = 0; k < EPT; k++) {
-                const uint32_t j = s0 + k * 256 + threadIdx.x;
-                if (j < s1) sdp[k >> 2] |= (uint32_t)side[j] << ((k & 3u) * 8);
-            }
+            if (j < s1) sdp[k >> 2] |= (uint32_t)side[j] << ((k & 3u) * 8);
         }
     }
-    auto entry = [&](unsigned k, uint32_t j) -> uint32_t {
-        if constexpr (LEAN)
-            return j < s1 ? part[j] : 0xffffffffu;
-        else
-            return ent[k];
-    };
     auto low_key = [&](unsigned k, uint32_t e) -> uint32_t {
         if constexpr (SIDE)
             return ((e >> P::SHIFT) & ((1u << LO4) - 1u)) | (((sdp[k >> 2] >> ((k & 3u) * 8)) & 0xffu) << LO4);
         else
             return (e >> P::SHIFT) & (LON - 1u);
     };
-#pragma clang loop unroll_count(LEAN ? 2 : EPT)
+#pragma clang loop unroll_count(EPT)
     for (unsigned k = 0; k < EPT; k++) {
         if (s0 + k * 256 >= s1) break; // workgroup-uniform
         const uint32_t j      = s0 + k * 256 + threadIdx.x;
         const bool     active = j < s1 && !((dropped >> k) & 1u);
-        const uint32_t key    = active ? low_key(k, entry(k, j)) : 0xffffffffu;
+        const uint32_t key    = active ? low_key(k, ent[k]) : 0xffffffffu;
         const uint32_t k0     = __builtin_amdgcn_readfirstlane(key);
         const uint64_t same   = __ballot(active && key == k0);
         if (active) {
@@ -1112,43 +743,25 @@ __global__ void __launch_bounds__(256) k_part_bins(const uint32_t* __restrict__ 
         }
     }
     k16_lds_sync();
-    if (MODE == 0 || (MODE == 2 && !single)) {
+    if (MODE == 0) {
         for (unsigned t = threadIdx.x; t < LON; t += 256) {
             const uint32_t v = h[t];
             if (v) atomicAdd(&counts_or_cursor[bin * LON + t], v);
         }
         return;
     }
-    if constexpr (MODE == 2) {
-        // counts of the bin's buckets, and their offsets by a local exclusive scan (LON <= 128 values)
-        const uint32_t v = h[threadIdx.x];
-        if (threadIdx.x < LON) counts_or_cursor[bin * LON + threadIdx.x] = v;
-        base[threadIdx.x] = v;
-        k16_lds_sync();
-        for (unsigned o = 1; o < 256; o <<= 1) {
-            uint32_t t = threadIdx.x >= o ? base[threadIdx.x - o] : 0u;
-            k16_lds_sync();
-            base[threadIdx.x] += t;
-            k16_lds_sync();
-        }
-        const uint32_t excl = base[threadIdx.x] - v;
-        k16_lds_sync();
-        base[threadIdx.x] = gstart[bin] + excl;
-        h[threadIdx.x]    = 0;
-    } else {
-        for (unsigned t = threadIdx.x; t < HN; t += 256) {
-            const uint32_t v = h[t];
-            base[t] = (t < LON && v) ? atomicAdd(&counts_or_cursor[bin * LON + t], v) : 0u;
-            h[t]    = 0;
-        }
+    for (unsigned t = threadIdx.x; t < HN; t += 256) {
+        const uint32_t v = h[t];
+        base[t] = (t < LON && v) ? atomicAdd(&counts_or_cursor[bin * LON + t], v) : 0u;
+        h[t]    = 0;
     }
     k16_lds_sync();
-#pragma clang loop unroll_count(LEAN ? 2 : EPT)
+#pragma clang loop unroll_count(EPT)
     for (unsigned k = 0; k < EPT; k++) {
         if (s0 + k * 256 >= s1) break;
         const uint32_t j      = s0 + k * 256 + threadIdx.x;
         const bool     active = j < s1 && !((dropped >> k) & 1u);
-        const uint32_t e      = entry(k, j);
+        const uint32_t e      = ent[k];
         const uint32_t key    = active ? low_key(k, e) : 0xffffffffu;
         const uint32_t k0     = __builtin_amdgcn_readfirstlane(key);
         const uint64_t same   = __ballot(active && key == k0);
@@ -1866,77 +1479,6 @@ __global__ void __launch_bounds__(128 * E::ALPP, E::ACC_MIN_WAVES) k_accumulate_
     }
 }
 
-// Persistent variant (K16_ACC_DYN = number of 128-thread workgroups): every wave takes the next 64 segments of the
-// longest-first order from a global counter, so a grid SMALLER than the chip's wave capacity stays balanced (the
-// grid-stride loop above does not: its workgroups own fixed slices) -- the point of a smaller grid being that the wave
-// slots and registers it does not take are free for the other lanes' sort / fold / reduction workgroups.
-// ctr[0] = next segment, ctr[1] = waves that have finished; the last wave to leave resets both.
-template <class E>
-__global__ void __launch_bounds__(128) k_accumulate_dyn(const typename E::Row* __restrict__ bases,
-                                                        const uint32_t* __restrict__ sorted,
-                                                        const uint32_t* __restrict__ off,
-                                                        const uint32_t* __restrict__ seg_off,
-                                                        const uint32_t* __restrict__ seg_bucket,
-                                                        const uint32_t* __restrict__ order,
-                                                        const uint32_t* __restrict__ total_segs,
-                                                        typename E::Pt* __restrict__ partial, uint32_t seg,
-                                                        uint32_t* __restrict__ ctr)
-{
-    const uint32_t nseg = *total_segs;
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t       t0   = 0;
-    if (lane == 0) t0 = atomicAdd(&ctr[0], 64u);
-    t0 = __builtin_amdgcn_readfirstlane(t0);
-    while (t0 < nseg) {
-        uint32_t nxt0 = 0;
-        if (lane == 0) nxt0 = atomicAdd(&ctr[0], 64u); // the next chunk's number arrives while this one is worked on
-        const uint32_t t = t0 + lane;
-        if (t < nseg) {
-            uint32_t s  = order[t];
-            uint32_t b  = seg_bucket[s];
-            uint32_t k  = s - seg_off[b];
-            uint32_t lo = off[b] + k * seg;
-            uint32_t hi = min(lo + seg, off[b + 1]);
-            auto gather = [&](uint32_t e) -> typename E::AffR { return E::load_row(&bases[e & 0x7fffffffu]); };
-            typename E::Acc  acc = E::acc_zero();
-            uint32_t         en  = sorted[lo];
-            typename E::AffR nxt = gather(en);
-            uint32_t         j   = lo;
-            if constexpr (E::has_aff_add) {
-                if (lo + 1 < hi) {
-                    const uint32_t   e2    = sorted[lo + 1];
-                    typename E::AffR first = (en >> 31) ? E::negate(nxt) : nxt, second = gather(e2);
-                    if (e2 >> 31) second = E::negate(second);
-                    if (lo + 2 < hi) {
-                        en  = sorted[lo + 2];
-                        nxt = gather(en);
-                    }
-                    acc = E::acc_from(E::add_aff(first, second));
-                    j   = lo + 2;
-                }
-            }
-            for (; j < hi; j++) {
-                typename E::AffR cur = nxt;
-                const uint32_t   ec  = en;
-                if (j + 1 < hi) {
-                    en  = sorted[j + 1];
-                    nxt = gather(en);
-                }
-                E::acc_madd(acc, cur, ec >> 31);
-            }
-            store_vec(&partial[s], E::acc_finish(acc));
-        }
-        t0 = __builtin_amdgcn_readfirstlane(nxt0);
-    }
-    if (lane == 0) {
-        const uint32_t waves = gridDim.x * (blockDim.x >> 6);
-        if (atomicAdd(&ctr[1], 1u) == waves - 1u) { // every wave has made its last (failed) fetch: nobody reads ctr[0] any more
-            ctr[0] = 0;
-            ctr[1] = 0;
-        }
-    }
-}
-
 // 16-lane shuffle of a whole point (tree fold of buckets with 5..16 segments)
 template <class T>
 __device__ __forceinline__ T shfl_down_vec(const T& v, unsigned delta, int width = 16)
@@ -1948,70 +1490,6 @@ __device__ __forceinline__ T shfl_down_vec(const T& v, unsigned delta, int width
 #pragma unroll
     for (unsigned i = 0; i < sizeof(T) / 4; i++) d[i] = (uint32_t)__shfl_down((int)s[i], delta, width);
     return r;
-}
-
-// Round 6: a segment walked by DIV lane pairs instead of one (G2 lane pairs only, E::ALPP == 2; K16_G2_ACC_SPLIT).  The
-// witness MSM's B2 accumulation is a few hundred waves, each a chain of up to 32 dependent G2 additions walked at a lone wave's
-// issue rate under the NTT passes -- 1.0-1.3 ms of LATENCY that the H MSM's start ends up waiting for (profiles/r06/
-// proof_timeline_8queues_variant0.txt).  Here pair `sub` of a segment's DIV pairs (adjacent lanes) adds the entries of its
-// DIV-th of the segment and the DIV partial sums are joined by a shuffle tree of log2(DIV) full additions: the chain is
-// seg / DIV + log2(DIV) links long, the sum is the same group element, the partial array keeps one point per segment.
-// skip == nullptr: every entry is live (k_accumulate); otherwise as k_accumulate_skip.
-template <class E, unsigned DIV>
-__global__ void __launch_bounds__(128 * E::ALPP, E::ACC_MIN_WAVES) k_accumulate_split(const typename E::Row* __restrict__ bases,
-                                                    const uint32_t* __restrict__ sorted,
-                                                    const uint32_t* __restrict__ off,
-                                                    const uint32_t* __restrict__ seg_off,
-                                                    const uint32_t* __restrict__ seg_bucket,
-                                                    const uint32_t* __restrict__ order,
-                                                    const uint32_t* __restrict__ total_segs,
-                                                    typename E::Pt* __restrict__ partial, uint32_t seg,
-                                                    const uint64_t* __restrict__ skip)
-{
-    static_assert(E::ALPP == 2 && (DIV == 2 || DIV == 4), "lane pairs, two or four pairs per segment");
-    constexpr unsigned LPS  = E::ALPP * DIV; // lanes per segment
-    const uint32_t     nseg = *total_segs;
-    const uint32_t     sub  = (threadIdx.x / E::ALPP) % DIV;
-    for (uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) / LPS; t < nseg; t += gridDim.x * blockDim.x / LPS) {
-        const uint32_t s   = order[t];
-        const uint32_t b   = seg_bucket[s];
-        const uint32_t k   = s - seg_off[b];
-        const uint32_t lo0 = off[b] + k * seg;
-        const uint32_t hi0 = min(lo0 + seg, off[b + 1]);
-        const uint32_t q   = (hi0 - lo0 + DIV - 1) / DIV;
-        const uint32_t lo  = min(lo0 + sub * q, hi0), hi = min(lo + q, hi0);
-        auto gather = [&](uint32_t e) -> typename E::ARow { return E::aload_row(&bases[e & 0x7fffffffu]); };
-        auto next_live = [&](uint32_t j, uint32_t* e) -> uint32_t {
-            while (j < hi) {
-                const uint32_t v = sorted[j], row = v & 0x7fffffffu;
-                if (!skip || !((skip[row >> 6] >> (row & 63u)) & 1ull)) {
-                    *e = v;
-                    return j;
-                }
-                j++;
-            }
-            return hi;
-        };
-        typename E::Acc  acc = E::acc_zero();
-        typename E::ARow nxt;
-        uint32_t         e = 0;
-        uint32_t         j = next_live(lo, &e);
-        if (j < hi) nxt = gather(e);
-        while (j < hi) {
-            typename E::ARow cur = nxt;
-            const uint32_t   ec  = e;
-            const uint32_t   j2  = next_live(j + 1, &e);
-            if (j2 < hi) nxt = gather(e);
-            E::acc_madd(acc, cur, ec >> 31);
-            j = j2;
-        }
-#pragma clang loop unroll(disable)
-        for (unsigned d = DIV / 2; d > 0; d >>= 1) { // all LPS lanes of the segment are here together (same t)
-            typename E::Acc o = shfl_down_vec(acc, d * E::ALPP, LPS);
-            acc               = E::tadd(acc, o);
-        }
-        if (sub == 0) E::acc_store(&partial[s], acc);
-    }
 }
 
 // One launch folds every size class (the lists come from k_scan2_apply); the role of a workgroup follows from its index:
@@ -2347,8 +1825,7 @@ struct SortArgs {
     const uint64_t* skip;  // bit i set: point i is left out (nullptr: none); k_part path only
     const void*     hs[3]; // non-null: d_scalars is still to be written -- scalar i = fromMontgomery(hs[0][i] * hs[1][i] - hs[2][i])
 };
-constexpr size_t SORT_GS  = 8208;        // >= NB1 + 1 for every partition config
-constexpr size_t SORT_GS8 = 8 * SORT_GS; // ... per XCD group (k_part X8)
+constexpr size_t SORT_GS = 8208; // >= NB1 + 1 for every partition config
 
 template <class Tick>
 int msm_sort_launch(k16_ctx* ctx, k16_ctx::Lane& L, hipStream_t st, const SortArgs& a, Tick&& tick)
@@ -2366,29 +1843,23 @@ int msm_sort_launch(k16_ctx* ctx, k16_ctx::Lane& L, hipStream_t st, const SortAr
     const void* conv_in  = a.conv_in;
     void*       conv_out = a.conv_out;
     const uint32_t* remap = a.remap;
-    // A zero-row mask is an optimisation -- a (0,0) row adds nothing (curve.cpp:185-250) -- and only the default partition
-    // sort implements it: the generic sort (n > 2^24, K16_ATOMIC_SORT) and the lean / write-combining variants sort ALL rows
-    // instead of refusing the MSM (round 4 returned K16_ERR_ARG here, which failed every proof of a key with more than 2^24
-    // wires, ADVICE r4).  The lane still records the mask it was ASKED for, so that a later MSM with the same mask reuses the
-    // (superset) sort.
-    const bool      mask_ok = (flat || (n <= (1u << 24) && !ctx->tune.atomic_sort)) && !ctx->lean_sort && !ctx->wc_sort;
-    const uint64_t* skip    = mask_ok ? a.skip : nullptr;
+    // A zero-row mask is an optimisation -- a (0,0) row adds nothing (curve.cpp:185-250) -- and only the partition sort
+    // implements it: the generic sort (n > 2^24, K16_ATOMIC_SORT) sorts ALL rows instead of refusing the MSM (round 4 returned
+    // K16_ERR_ARG here, which failed every proof of a key with more than 2^24 wires, ADVICE r4).  The lane still records the
+    // mask it was ASKED for, so that a later MSM with the same mask reuses the (superset) sort.
+    const bool      use_part = flat || (n <= (1u << 24) && !ctx->tune.atomic_sort);
+    const uint64_t* skip     = use_part ? a.skip : nullptr;
     constexpr size_t GS  = SORT_GS;
     {
         k16_stat_scope ss(ctx, "msm_sort", st);
         tick("pre");
         K16_HIP(ctx, hipMemsetAsync(zr, 0, zr_words * 4, st));
-        if (ctx->wait_after_memset) { // (K16_H_WAIT_FIRST: the scalars are not ready yet, the tables can be cleared meanwhile)
-            K16_HIP(ctx, hipStreamWaitEvent(st, ctx->wait_after_memset, 0));
-            ctx->wait_after_memset = nullptr;
-        }
         tick("memset");
-        const bool use_part = flat || (n <= (1u << 24) && !ctx->tune.atomic_sort);
+        // five-byte entries + LDS-staged scatter (k_part_stage): the H MSM's sort (flat, c = 20) and the 2^20 x c16 MSM
+        const bool staged = use_part && !skip && n >= (1u << 16) && ((flat && c == 20) || (!flat && c == 16 && n < (1u << 24)));
         // the scalars of the prover's H MSM: formed by the staged fixed-base sort's counting pass (below), by a kernel of their
         // own in front of every other sort
-        const bool        hs_fused   = a.hs[0] && use_part && flat && c == 20 && n >= (1u << 16) && !skip &&
-                              !a.conv_in && !ctx->lean_sort && !ctx->wc_sort && !ctx->tune.no_staged_sort &&
-                              !ctx->tune.fused_bins;
+        const bool hs_fused = a.hs[0] && staged && flat && !a.conv_in;
         if (a.hs[0] && !hs_fused)
             hipLaunchKernelGGL(k_hs_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (uint4*)const_cast<void*>(d_scalars), n,
                                (const k16::Fr*)a.hs[0], (const k16::Fr*)a.hs[1], (const k16::Fr*)a.hs[2]);
@@ -2406,22 +1877,15 @@ int msm_sort_launch(k16_ctx* ctx, k16_ctx::Lane& L, hipStream_t st, const SortAr
                                seg_hist);
         };
         if (use_part) {
-            // bin starts and slice table (written by workgroup 0 of the scatter pass), then the partition itself
-            if ((rc = k16_ws_reserve(ctx, L.ws_lvl_d, (2 * GS + SORT_GS8) * 4 + (size_t)n * W * 5 + 64))) return rc;
-            uint32_t* gstart  = (uint32_t*)L.ws_lvl_d.p;
-            uint32_t* gslice  = gstart + GS;
-            uint32_t* gstart8 = gstart + 2 * GS;
-            uint32_t* part    = gstart8 + SORT_GS8;
-            const bool x8 = ctx->tune.x8; // per-XCD sub-regions of every bin: measured, no effect on the write traffic (k_part), off
-
-            // measured at 2^20, c = 16: the fused pass is SLOWER than count + scatter (sort 0.534 vs 0.501 ms, 628 vs 654 M points/s
-            // pipelined): the separate counting pass is a pure streaming read that leaves the entries in L2 for the scatter
-            // pass, and the fused workgroup serialises histogram -> scan -> rank.  Kept behind K16_FUSED_BINS=1.
-            const bool fuse_bins = ctx->tune.fused_bins;
-            const bool        lean      = ctx->lean_sort;
-            // the write-combining scatter pass pays for large uniform MSMs (c >= 13: few windows x many bins); small ones keep
-            // the 2048-point tiles (more workgroups than CUs)
-            const bool        wc        = ctx->wc_sort && !lean && c >= 13 && n >= (1u << 18);
+            // bin starts and slice table, then the partition itself
+            if ((rc = k16_ws_reserve(ctx, L.ws_lvl_d, 2 * GS * 4 + (size_t)n * W * 5 + 64))) return rc;
+            uint32_t* gstart = (uint32_t*)L.ws_lvl_d.p;
+            uint32_t* gslice = gstart + GS;
+            uint32_t* part   = gstart + 2 * GS;
+            // Plain partition: counting pass, scatter pass (which scans the bin counts itself and whose workgroup 0 writes the
+            // bin starts and the slice table), bucket counts, scans, final scatter.  Count + scatter beats one fused pass: the
+            // counting pass is a pure streaming read that leaves the entries in L2 for the scatter pass, and a fused workgroup
+            // serialises histogram -> scan -> rank (DESIGN_HISTORY.md).
 #define K16_PART(CC) K16_PART_CFG(CC, PartCfg<CC>)
 #define K16_PART_CFG(CC, CFG)                                                                                     \
     case CC: {                                                                                                   \
@@ -2430,18 +1894,7 @@ int msm_sort_launch(k16_ctx* ctx, k16_ctx::Lane& L, hipStream_t st, const SortAr
         const unsigned pgrid  = std::min<unsigned>(ntiles, 256 * 4);                                             \
         const unsigned sgrid = nb1 + (unsigned)(((uint64_t)n * W) / PART_SLICE) + 1;                              \
         static_assert(CFG::NB1 + 1 <= GS, "partition tables too small");                                         \
-        const bool use_x8 = x8 && !wc && !lean;                                                                  \
-        if (conv_in && use_x8)                                                                                   \
-            hipLaunchKernelGGL((k_part<CFG, false, true, true>), dim3(pgrid), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st, \
-                               (const uint4*)d_scalars, n, gcount, part, (const k16::Aff<k16::Fq>*)conv_in,            \
-                               (k16::Aff<k16::Fq>*)conv_out, (const uint32_t*)nullptr, (uint32_t*)nullptr,             \
-                               (uint32_t*)nullptr, skip);                                                                  \
-        else if (use_x8)                                                                                         \
-            hipLaunchKernelGGL((k_part<CFG, false, false, true>), dim3(pgrid), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st, \
-                               (const uint4*)d_scalars, n, gcount, part, (const k16::Aff<k16::Fq>*)nullptr,            \
-                               (k16::Aff<k16::Fq>*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,              \
-                               (uint32_t*)nullptr, skip);                                                                  \
-        else if (conv_in)                                                                                        \
+        if (conv_in)                                                                                             \
             hipLaunchKernelGGL((k_part<CFG, false, true>), dim3(pgrid), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st,     \
                                (const uint4*)d_scalars, n, gcount, part, (const k16::Aff<k16::Fq>*)conv_in,            \
                                (k16::Aff<k16::Fq>*)conv_out, (const uint32_t*)nullptr, (uint32_t*)nullptr,             \
@@ -2451,59 +1904,13 @@ int msm_sort_launch(k16_ctx* ctx, k16_ctx::Lane& L, hipStream_t st, const SortAr
                                (const uint4*)d_scalars, n, gcount, part, (const k16::Aff<k16::Fq>*)nullptr,            \
                                (k16::Aff<k16::Fq>*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,              \
                                (uint32_t*)nullptr, skip);                                                                  \
-        if (wc) {                                                                                                \
-            const unsigned wtiles = (unsigned)((n + CFG::WC_TILE - 1) / CFG::WC_TILE);                           \
-            const unsigned wlds   = WcGeom<CFG>::LDS_WORDS * 4;                                                  \
-            static bool    wc_attr = false;                                                                      \
-            if (!wc_attr) {                                                                                      \
-                K16_HIP(ctx, hipFuncSetAttribute((const void*)k_part_wc<CFG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                 (int)wlds));                                                    \
-                wc_attr = true;                                                                                  \
-            }                                                                                                    \
-            hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(WC_THREADS), 0, st, (const uint32_t*)gcount, nb1, gstart, gslice); \
-            hipLaunchKernelGGL((k_part_wc<CFG>), dim3(wtiles), dim3(WC_THREADS), wlds, st, (const uint4*)d_scalars, n, \
-                               gcursor, part, (const uint32_t*)gstart);                                          \
-            hipLaunchKernelGGL((k_part_bins<CFG, 0>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, counts, \
-                               sorted, 0u, remap);                                                               \
-            scans();                                                                                             \
-            hipLaunchKernelGGL((k_part_bins<CFG, 1>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, cursor, \
-                               sorted, 0u, remap);                                                               \
-            break;                                                                                               \
-        }                                                                                                        \
-        if (lean) {                                                                                              \
-            hipLaunchKernelGGL((k_part_scatter_lean<CFG>), dim3(ntiles), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st,    \
-                               (const uint4*)d_scalars, n, gcursor, part, (const uint32_t*)gcount, gstart, gslice);    \
-            hipLaunchKernelGGL((k_part_bins<CFG, 0, true>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, \
-                               counts, sorted, 0u, remap);                                                       \
-            scans();                                                                                             \
-            hipLaunchKernelGGL((k_part_bins<CFG, 1, true>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, \
-                               cursor, sorted, 0u, remap);                                                       \
-            break;                                                                                               \
-        }                                                                                                        \
-        if (use_x8) {                                                                                            \
-            hipLaunchKernelGGL(k_bin_starts8, dim3(1), dim3(1024), 0, st, (const uint32_t*)gcount, nb1, gstart8, gstart, gslice); \
-            hipLaunchKernelGGL((k_part<CFG, true, false, true>), dim3(ntiles), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st, \
-                               (const uint4*)d_scalars, n, gcursor, part, (const k16::Aff<k16::Fq>*)nullptr,      \
-                               (k16::Aff<k16::Fq>*)nullptr, (const uint32_t*)gstart8, gstart, gslice, skip);            \
-        } else                                                                                                   \
         hipLaunchKernelGGL((k_part<CFG, true>), dim3(ntiles), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st, (const uint4*)d_scalars, n, \
                            gcursor, part, (const k16::Aff<k16::Fq>*)nullptr, (k16::Aff<k16::Fq>*)nullptr,         \
                            (const uint32_t*)gcount, gstart, gslice, skip);                                              \
-        if (fuse_bins) {                                                                                         \
-            hipLaunchKernelGGL((k_part_bins<CFG, 2>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, counts, \
-                               sorted, 0u, remap);                                                               \
-        } else {                                                                                                 \
-            hipLaunchKernelGGL((k_part_bins<CFG, 0>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, counts, \
-                               sorted, 0u, remap);                                                               \
-        }                                                                                                        \
+        hipLaunchKernelGGL((k_part_bins<CFG, 0>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, counts, sorted, remap); \
         scans();                                                                                                 \
-        hipLaunchKernelGGL((k_part_bins<CFG, 1>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, cursor, \
-                           sorted, fuse_bins ? 1u : 0u, remap);                                                  \
+        hipLaunchKernelGGL((k_part_bins<CFG, 1>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, cursor, sorted, remap); \
     } break;
-            // five-byte entries + LDS-staged scatter (k_part_stage): the H MSM's sort (flat, c = 20) and the 2^20 x c16 MSM
-            const bool staged_on = !ctx->tune.no_staged_sort;
-            const bool        staged    = staged_on && !wc && !lean && !fuse_bins && !skip && n >= (1u << 16) &&
-                                   ((flat && c == 20) || (!flat && c == 16 && n < (1u << 24)));
 #define K16_PART_STAGED(CFG)                                                                                      \
     {                                                                                                            \
         const unsigned nb1    = CFG::NB1;                                                                        \
@@ -2521,7 +1928,7 @@ int msm_sort_launch(k16_ctx* ctx, k16_ctx::Lane& L, hipStream_t st, const SortAr
         }                                                                                                        \
         uint8_t* part1 = (uint8_t*)(part + (size_t)n * W);                                                       \
         if (hs_fused)                                                                                            \
-            hipLaunchKernelGGL((k_part<CFG, false, false, false, true>), dim3(pgrid), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st, \
+            hipLaunchKernelGGL((k_part<CFG, false, false, true>), dim3(pgrid), dim3(256), ((nb1 + 1) / 2 + nb1) * 4, st, \
                                (const uint4*)d_scalars, n, gcount, part, (const k16::Aff<k16::Fq>*)nullptr,       \
                                (k16::Aff<k16::Fq>*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, \
                                (const uint64_t*)nullptr, (const k16::Fr*)a.hs[0], (const k16::Fr*)a.hs[1],       \
@@ -2545,10 +1952,10 @@ int msm_sort_launch(k16_ctx* ctx, k16_ctx::Lane& L, hipStream_t st, const SortAr
         }                                                                                                        \
         hipLaunchKernelGGL((k_bins_stage<CFG>), dim3(nb1), dim3(BS_THREADS), blds, st, (const uint32_t*)gstart, nb1,         \
                            (const uint32_t*)part, (const uint8_t*)part1, counts, sorted, remap);                 \
-        hipLaunchKernelGGL((k_part_bins<CFG, 0>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, counts, sorted, 0u, \
+        hipLaunchKernelGGL((k_part_bins<CFG, 0>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, counts, sorted,     \
                            remap, (const uint8_t*)part1, BS_CAP);                                                \
         scans();                                                                                                 \
-        hipLaunchKernelGGL((k_part_bins<CFG, 1>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, cursor, sorted, 0u, \
+        hipLaunchKernelGGL((k_part_bins<CFG, 1>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, cursor, sorted,     \
                            remap, (const uint8_t*)part1, BS_CAP);                                                \
     }
             if (staged && flat) {
@@ -2602,10 +2009,10 @@ int msm_sort_plan(k16_ctx* ctx, k16_ctx::Lane& SL, const void* d_scalars, uint64
     int            rc;
     const unsigned W  = flat ? (257 + c - 1) / c : n_windows(c);
     const uint32_t nb = flat ? (1u << (c - 1)) : (W << (c - 1)); // buckets (w, magnitude - 1) or magnitude - 1
-    // Zeroed region of a sort (ONE memset): misc[16] | bin counts[8][GS] | bin cursors[8][GS] | segment-length histogram and
+    // Zeroed region of a sort (ONE memset): misc[16] | bin counts[GS] | bin cursors[GS] | segment-length histogram and
     // cursors [2 x (MAX_SEG+1)] | bucket counts[nb+1]
-    constexpr size_t GS8    = SORT_GS8;
-    constexpr size_t ZR_HDR = (16 + 2 * GS8 + 2 * (MAX_SEG + 1) + 3) & ~(size_t)3;
+    constexpr size_t GS     = SORT_GS;
+    constexpr size_t ZR_HDR = (16 + 2 * GS + 2 * (MAX_SEG + 1) + 3) & ~(size_t)3;
     const size_t     zr_words = ZR_HDR + nb + 1;
     if (!reuse) {
         if ((rc = k16_ws_reserve(ctx, SL.ws_counts, zr_words * 4))) return rc;
@@ -2647,8 +2054,8 @@ int msm_sort_plan(k16_ctx* ctx, k16_ctx::Lane& SL, const void* d_scalars, uint64
     a.zr         = zr;
     a.misc       = zr;                 // [0] total entries, [1] total segs, [2] medium, [3] giant, [4] tree count
     a.gcount     = zr + 16;
-    a.gcursor    = zr + 16 + GS8;
-    a.seg_hist   = zr + 16 + 2 * GS8;  // [MAX_SEG+1] histogram of segment lengths, then [MAX_SEG+1] cursors
+    a.gcursor    = zr + 16 + GS;
+    a.seg_hist   = zr + 16 + 2 * GS;  // [MAX_SEG+1] histogram of segment lengths, then [MAX_SEG+1] cursors
     a.counts     = zr + ZR_HDR;
     a.offsets    = (uint32_t*)SL.ws_offsets.p;
     a.cursor     = (uint32_t*)SL.ws_cursor.p;
@@ -2672,9 +2079,7 @@ int msm_sort_plan(k16_ctx* ctx, k16_ctx::Lane& SL, const void* d_scalars, uint64
 static bool msm_sort_is_plain_partition(const k16_ctx* ctx, uint64_t n, unsigned c, bool flat, const uint64_t* skip)
 {
     if (flat || n > (1u << 24) || c < 4 || c > 16 || ctx->tune.atomic_sort) return false;
-    if (ctx->lean_sort || (ctx->wc_sort && c >= 13 && n >= (1u << 18))) return false;
-    if (ctx->tune.x8 || ctx->tune.fused_bins) return false;
-    const bool staged = !ctx->tune.no_staged_sort && !skip && n >= (1u << 16) && c == 16 && n < (1u << 24);
+    const bool staged = !skip && n >= (1u << 16) && c == 16 && n < (1u << 24);
     return !staged;
 }
 
@@ -2687,7 +2092,7 @@ int msm_sort_derive_launch(k16_ctx* ctx, hipStream_t st, const SortArgs& a, cons
 {
     const uint32_t*  gstart = (const uint32_t*)owner.ws_lvl_d.p;
     const uint32_t*  gslice = gstart + SORT_GS;
-    const uint32_t*  part   = gstart + 2 * SORT_GS + SORT_GS8;
+    const uint32_t*  part   = gstart + 2 * SORT_GS;
     k16_stat_scope   ss(ctx, "msm_sort", st);
     K16_HIP(ctx, hipMemsetAsync(a.zr, 0, a.zr_words * 4, st));
     constexpr unsigned SCAN_BLK = SCAN_T * SCAN_PER_DEFAULT;
@@ -2702,13 +2107,13 @@ int msm_sort_derive_launch(k16_ctx* ctx, hipStream_t st, const SortArgs& a, cons
         typedef PartCfg<CC> CFG;                                                                                             \
         const unsigned      nb1 = CFG::NB1, sgrid = nb1 + sgrid_max;                                                         \
         hipLaunchKernelGGL((k_part_bins<CFG, 0>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, a.counts, a.sorted, \
-                           0u, a.remap, (const uint8_t*)nullptr, 0u, drop);                                                  \
+                           a.remap, (const uint8_t*)nullptr, 0u, drop);                                                      \
         hipLaunchKernelGGL(k_scan2_totals<SCAN_PER_DEFAULT>, dim3(nblk), dim3(SCAN_T), 0, st, a.counts, a.nb, a.seg, a.scan_tmp); \
         hipLaunchKernelGGL(k_scan2_apply<SCAN_PER_DEFAULT>, dim3(nblk), dim3(SCAN_T), 0, st, a.counts, a.nb, a.seg, a.scan_tmp, \
                            a.offsets, a.cursor, a.seg_off, a.misc, a.big_list, a.big_cap, a.big_list + a.big_cap,            \
                            a.big_list + a.big_cap + GIANT_CAP, a.seg_bucket, a.seg_hist);                                    \
         hipLaunchKernelGGL((k_part_bins<CFG, 1>), dim3(sgrid), dim3(256), 0, st, gstart, gslice, nb1, part, a.cursor, a.sorted, \
-                           0u, a.remap, (const uint8_t*)nullptr, 0u, drop);                                                  \
+                           a.remap, (const uint8_t*)nullptr, 0u, drop);                                                      \
     } break;
     switch (a.c) {
         K16_DERIVE(4) K16_DERIVE(5) K16_DERIVE(6) K16_DERIVE(7) K16_DERIVE(8) K16_DERIVE(9) K16_DERIVE(10) K16_DERIVE(11)
@@ -2882,49 +2287,17 @@ int msm_enqueue_t(k16_ctx* ctx, const typename E::Row* d_bases, const void* d_sc
     }
     tk.tick("sorted");
     K16_TRACE_PT("sorted");
-    if (ctx->serialize_acc) {
-        hipEvent_t prev = ctx->acc_fence_mode == 2 ? ctx->last_tail_done : ctx->acc_fence_mode == 1 ? ctx->last_lvl1_done
-                                                                                                    : ctx->last_acc_done;
-        hipEvent_t mine = ctx->acc_fence_mode == 2 ? L.tail_done : ctx->acc_fence_mode == 1 ? L.lvl1_done : L.acc_done;
-        if (prev && prev != mine) K16_HIP(ctx, hipStreamWaitEvent(st, prev, 0));
-    }
+    if (ctx->serialize_acc && ctx->last_acc_done && ctx->last_acc_done != L.acc_done)
+        K16_HIP(ctx, hipStreamWaitEvent(st, ctx->last_acc_done, 0));
     {
         k16_stat_scope ss(ctx, "msm_accumulate", st);
-        unsigned grid = (unsigned)std::min<size_t>((max_segs + 127) / 128, 256 * 64);
-        if (ctx->acc_grid_cap) grid = std::min(grid, ctx->acc_grid_cap);
-        bool launched = false;
-        if constexpr (E::ALPP == 1) { // (the dynamic-fetch lab variant hands out 64 segments per wave: one lane per segment)
-            if (ctx->acc_dyn_grid) {
-                const bool fresh = L.ws_misc.bytes == 0;
-                if ((rc = k16_ws_reserve(ctx, L.ws_misc, 64))) return rc;
-                if (fresh) K16_HIP(ctx, hipMemsetAsync(L.ws_misc.p, 0, 64, st));
-                hipLaunchKernelGGL((k_accumulate_dyn<E>), dim3(std::min(grid, ctx->acc_dyn_grid)), dim3(128), ctx->acc_lds_bytes, st,
-                                   d_bases, sorted, offsets, seg_off, seg_bucket, seg_order, misc + 1, partial, seg,
-                                   (uint32_t*)L.ws_misc.p);
-                launched = true;
-            }
-        }
-        // K16_G2_ACC_SPLIT (round 6): the witness MSMs' G2 accumulation with two / four lane pairs per segment (k_accumulate_split)
-        if constexpr (E::ALPP == 2) {
-            const int split = ctx->forced_seg ? ctx->tune.g2_acc_split : 1;
-            if (!launched && (split == 2 || split == 4)) {
-                const unsigned g2 = (unsigned)std::min<size_t>((size_t)grid * split, 256 * 256);
-                if (split == 2)
-                    hipLaunchKernelGGL((k_accumulate_split<E, 2>), dim3(g2), dim3(128 * E::ALPP), ctx->acc_lds_bytes, st, d_bases, sorted,
-                                       offsets, seg_off, seg_bucket, seg_order, misc + 1, partial, seg, acc_skip);
-                else
-                    hipLaunchKernelGGL((k_accumulate_split<E, 4>), dim3(g2), dim3(128 * E::ALPP), ctx->acc_lds_bytes, st, d_bases, sorted,
-                                       offsets, seg_off, seg_bucket, seg_order, misc + 1, partial, seg, acc_skip);
-                launched = true;
-            }
-        }
-        if (launched) {
-        } else if (acc_skip)
-            hipLaunchKernelGGL((k_accumulate_skip<E>), dim3(grid), dim3(128 * E::ALPP), ctx->acc_lds_bytes, st, d_bases, sorted, offsets, seg_off,
+        const unsigned grid = (unsigned)std::min<size_t>((max_segs + 127) / 128, 256 * 64);
+        if (acc_skip)
+            hipLaunchKernelGGL((k_accumulate_skip<E>), dim3(grid), dim3(128 * E::ALPP), 0, st, d_bases, sorted, offsets, seg_off,
                                seg_bucket, seg_order, misc + 1, partial, seg, acc_skip);
         else
-        hipLaunchKernelGGL((k_accumulate<E>), dim3(grid), dim3(128 * E::ALPP), ctx->acc_lds_bytes, st, d_bases, sorted, offsets, seg_off,
-                           seg_bucket, seg_order, misc + 1, partial, seg);
+            hipLaunchKernelGGL((k_accumulate<E>), dim3(grid), dim3(128 * E::ALPP), 0, st, d_bases, sorted, offsets, seg_off,
+                               seg_bucket, seg_order, misc + 1, partial, seg);
     }
     if (ctx->serialize_acc) {
         K16_HIP(ctx, hipEventRecord(L.acc_done, st));
@@ -2939,7 +2312,6 @@ int msm_enqueue_t(k16_ctx* ctx, const typename E::Row* d_bases, const void* d_sc
     // M = 2^mlog slots per lane: as many as the cap allows, but keep at least ~16 k lanes in flight
     uint32_t mlog = std::min<uint32_t>(ctx->wsum_mlog_cap, WSUM_MLOG_MAX);
     while (mlog > 0 && (((uint64_t)Wr * win_mag) >> mlog) < 16384) mlog--;
-    if (ctx->tune.wsum_mlog >= 0) mlog = std::min<uint32_t>((uint32_t)ctx->tune.wsum_mlog, std::min<uint32_t>(WSUM_MLOG_MAX, c - 1));
     const uint32_t U     = win_mag >> mlog; // digit magnitudes 1 .. win_mag, M per lane (c >= 4)
     uint32_t       nbits = 0;
     while ((1u << nbits) < U) nbits++;
@@ -2977,23 +2349,14 @@ int msm_enqueue_t(k16_ctx* ctx, const typename E::Row* d_bases, const void* d_sc
         unsigned nthr = 2 * Wr * U; // lane pairs
         // the prefetching variant for the single MSM on a proof's critical path (the fixed-base H MSM); the pipelined MSMs and
         // the witness MSMs keep the two-point version (fewer registers beside other lanes' kernels)
-        const bool l1_prefetch = !ctx->tune.no_l1_prefetch;
-        if (flat && l1_prefetch && sizeof(typename E::Pt) < 200)
+        if (flat && sizeof(typename E::Pt) < 200)
             hipLaunchKernelGGL((k_wsum_level1<E, true>), dim3((nthr + 63) / 64), dim3(64 * E::LPP), 0, st, U, Wr, 1u << mlog, seg_off, c,
                                flat ? 1u : 0u, partial, S, G);
         else
-        hipLaunchKernelGGL((k_wsum_level1<E>), dim3((nthr + 63) / 64), dim3(64 * E::LPP), 0, st, U, Wr, 1u << mlog, seg_off, c,
-                           flat ? 1u : 0u, partial, S, G);
-        if (ctx->serialize_acc && ctx->acc_fence_mode == 1 && !ctx->capturing) {
-            K16_HIP(ctx, hipEventRecord(L.lvl1_done, st));
-            ctx->last_lvl1_done = L.lvl1_done;
-        }
+            hipLaunchKernelGGL((k_wsum_level1<E>), dim3((nthr + 63) / 64), dim3(64 * E::LPP), 0, st, U, Wr, 1u << mlog, seg_off, c,
+                               flat ? 1u : 0u, partial, S, G);
         hipLaunchKernelGGL((k_wsum_bits<E>), dim3(Wr * (nbits + 2)), dim3(256 * E::LPP), 256 * sizeof(typename E::Pt), st, S, G, U, nbits,
                            T);
-        if (ctx->serialize_acc && ctx->acc_fence_mode == 2 && !ctx->capturing) {
-            K16_HIP(ctx, hipEventRecord(L.tail_done, st));
-            ctx->last_tail_done = L.tail_done;
-        }
         tk.tick("wsum");
     }
     tk.tick("d2h");
@@ -3124,9 +2487,7 @@ int msm_enqueue_classified_t(k16_ctx* ctx, const typename E::Row* d_rows, const 
     K16_HIP(ctx, hipStreamWaitEvent(st, cls->built, 0));
     // entries per lane of a masked sum: a chain of K dependent additions, then the trees.  Longer chains are less work per
     // entry (the trees' 255 full additions per 256 * K mixed ones), shorter ones finish sooner; G2 additions take 3x as long
-    const unsigned K1 = ctx->tune.narrow_chain ? (unsigned)std::max(1, std::min(1024, ctx->tune.narrow_chain)) : 32u;
-    const unsigned K2 = ctx->tune.narrow_chain_g2 ? (unsigned)std::max(1, std::min(1024, ctx->tune.narrow_chain_g2)) : 16u;
-    const unsigned K = sizeof(typename E::Pt) > 200 ? K2 : K1;
+    const unsigned K = sizeof(typename E::Pt) > 200 ? 16u : 32u; // G2 : G1
     const uint64_t max_chunks = ((uint64_t)NARROW_BITS * cls->n + 256ull * K - 1) / (256ull * K) + NARROW_BITS;
     if ((rc = k16_ws_reserve(ctx, L.ws_narrow, 64 + max_chunks * sizeof(typename E::Pt)))) return rc;
     uint32_t*       chunk_tab = (uint32_t*)L.ws_narrow.p;

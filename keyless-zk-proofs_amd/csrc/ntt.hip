@@ -11,14 +11,6 @@
 #include "ctx.h"
 #include "bn254_fq9.h"
 
-#ifndef K16_CHAIN_PRIO
-// Wave priority of the polynomial chain's kernels.  3 (above everything) until round 6; the witness MSMs' short kernels run at 3
-// too and their accumulations at 0.  With the chain at 1 it still wins against the accumulations it runs beside, but the
-// witness MSMs' fold / weighted-sum tails -- whose end, not the chain's, is what the H accumulation's start waits for -- are no
-// longer held up by NTT waves: p50 over 11 alternating runs on two boxes 5.35-5.57 (median 5.46) against 5.37-5.84 (5.67) ms, equal on
-// a third, two provers unchanged (profiles/r06/ab_wave_priorities.log, ab_chain_priority_second_box.log).  -DK16_CHAIN_PRIO=n to compare.
-#define K16_CHAIN_PRIO 1
-#endif
 using namespace k16;
 
 namespace {
@@ -65,22 +57,6 @@ __global__ void __launch_bounds__(256) k_bitrev(Fr* __restrict__ a, uint32_t log
         st_fr(&a[i], y);
         st_fr(&a[r], x);
     }
-}
-
-// fft.cpp:197-218 : one DIT stage, n/2 butterflies
-__global__ void __launch_bounds__(256) k_stage(Fr* __restrict__ a, const Fr* __restrict__ roots, uint32_t logn,
-                                               uint32_t s, uint32_t S)
-{
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (1u << (logn - 1))) return;
-    uint32_t md2 = 1u << (s - 1);
-    uint32_t j   = i & (md2 - 1);
-    uint32_t k   = (i >> (s - 1)) << s;
-    Fr       w   = ld_fr(&roots[(size_t)j << (S - s)]);
-    Fr       t   = fmul(w, ld_fr(&a[k + j + md2]));
-    Fr       u   = ld_fr(&a[k + j]);
-    st_fr(&a[k + j], fadd(t, u));
-    st_fr(&a[k + j + md2], fsub(u, t));
 }
 
 // Fused radix-2^K passes (k_ntt_pass9 below): stages s0+1 .. s0+K of the same DIT network (fft.cpp:197-218)
@@ -401,7 +377,7 @@ int k16_ntt_get_table(k16_ctx* ctx, uint64_t max_domain, k16_ntt_table** out)
 
 // the fused passes of one transform over `count` polynomials; tail_dst != nullptr: the last pass stores through the TAIL path
 static void ntt_passes(k16_ctx* ctx, Fr* const* polys, int count, uint32_t logn, k16_ntt_table* tab, bool packed9,
-                       Fr* const* tail_dst, const Fr* shift9, hipStream_t st, uint32_t tile_log = 10)
+                       Fr* const* tail_dst, const Fr* shift9, hipStream_t st)
 {
     NttPtrs pp = {};
     for (int i = 0; i < count; i++) {
@@ -410,15 +386,13 @@ static void ntt_passes(k16_ctx* ctx, Fr* const* polys, int count, uint32_t logn,
     }
     const uint64_t  n      = 1ull << logn;
     uint32_t        s0     = 0;
-    const uint32_t* stage9 = ctx->tune.ntt_no_stage_tables ? nullptr : tab->stage9;
-    // Tile size.  1024 elements (36 KB of LDS, four workgroups per CU): 21 stages are three passes (10 + 6 + 5, 512-byte runs).
-    // K16_NTT_TILE_LOG=11: 2048 elements (72 KB, two workgroups of 512 threads per CU), two passes (11 + 10) -- one load /
-    // store round trip less per transform, but the second pass then moves 64-byte runs (T = 2: a tile is T x 2^10 elements
-    // whatever the layout between the passes).  Measured in a proof (three polynomials per launch, 2^21, round 4): forward
-    // 395 + 684 us against 610 + 349 + 300, the inverse with its TAIL store 372 + 1194 against 309 + 393 + 450; proof p50
-    // 6.03-6.18 (both), 5.85-6.06 (forward only) against 5.86-6.05 ms: no gain, so 1024 stays the default.
-    if (tail_dst && ctx->tune.ntt_tail_small) tile_log = 10;
-    const uint32_t TLMAX = tile_log == 11 ? 1u : 4u;
+    const uint32_t* stage9 = tab->stage9;
+    // Tile size: 1024 elements (36 KB of LDS, four workgroups of 256 threads per CU): 21 stages are three passes (10 + 6 + 5,
+    // 512-byte runs).  2048-element tiles make that two passes, but the second then moves 64-byte runs: measured, no gain
+    // (DESIGN_HISTORY.md).
+    constexpr uint32_t tile_log = 10, TLMAX = 4;
+    static_assert((sizeof(Fr9) << tile_log) + (((size_t)1 << tile_log) >> 6) * 4 + 16 <= 48 * 1024,
+                  "a tile (TL + K <= tile_log below) plus the TAIL padding fits the default LDS limit");
     while (s0 < logn) {
         uint32_t       TL = s0 < TLMAX ? s0 : TLMAX;                    // T = min(2^s0, 16) lo values per tile
         const uint32_t K  = std::min<uint32_t>(logn - s0, tile_log - TL); // <= 2^tile_log elements per tile
@@ -426,21 +400,20 @@ static void ntt_passes(k16_ctx* ctx, Fr* const* polys, int count, uint32_t logn,
         // T = 16 its tiles had 512 elements -- 128 quads for 256 lanes, so the two double stages of its three rounds ran on
         // half of the workgroup (the pass sat at 0.60 of its issue bound, profiles/r04/pmc_ntt_passes.txt); T = 32 gives every lane
         // its four elements and 1 KB runs (round 5)
-        if (TL + K < tile_log && !ctx->tune.ntt_tail_small) TL = std::min<uint32_t>(s0, tile_log - K);
+        if (TL + K < tile_log) TL = std::min<uint32_t>(s0, tile_log - K);
         const bool     first = s0 == 0, last = s0 + K == logn;
         const bool     cin = !packed9 && first, cout = !packed9 && last, tail = tail_dst && last;
         const dim3     grid((unsigned)(n >> (K + TL)), (unsigned)count);
         const size_t   telem = (size_t)1 << (TL + K);
         const size_t   lds   = telem * sizeof(Fr9) + (tail ? (telem >> 6) * 4 + 16 : 0);
-        const bool     big = lds > 48 * 1024; // 512 threads per workgroup, dynamic LDS above the default limit
-        // K16_OPT_SHARED_GPU / K16_NTT_WG_PER_CU=3: the 1024-element passes ask for a third of the CU's LDS instead of the 36 KB
+        // K16_OPT_SHARED_GPU: the 1024-element passes ask for a third of the CU's LDS instead of the 36 KB
         // they use, so that three workgroups are resident per CU instead of four -- 312 of a SIMD's 512 registers, which leaves
         // room for a wave of a bucket accumulation (159) beside them
         const unsigned wg_per_cu = ctx->ntt_wg_per_cu;
-        const size_t lds_launch = (!big && wg_per_cu < 4) ? std::max<size_t>(lds, (size_t)(160 * 1024 / wg_per_cu) - 1024) : lds;
+        const size_t lds_launch = wg_per_cu < 4 ? std::max<size_t>(lds, (size_t)(160 * 1024 / wg_per_cu) - 1024) : lds;
 #define K16_NTT_LAUNCH(CI, CO, TA)                                                                                              \
     do {                                                                                                                        \
-        if (!big && lds_launch > lds) {                                                                                         \
+        if (lds_launch > lds) {                                                                                                 \
             static bool attr2 = false;                                                                                          \
             if (!attr2) {                                                                                                       \
                 (void)hipFuncSetAttribute((const void*)k_ntt_pass9<CI, CO, TA, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, \
@@ -449,15 +422,6 @@ static void ntt_passes(k16_ctx* ctx, Fr* const* polys, int count, uint32_t logn,
             }                                                                                                                   \
             hipLaunchKernelGGL((k_ntt_pass9<CI, CO, TA, 256>), grid, dim3(256), lds_launch, st, pp, tab->roots9, s0, K, TL,     \
                                tab->s, logn, shift9, stage9);                                                                   \
-        } else if (big) {                                                                                                              \
-            static bool attr = false;                                                                                           \
-            if (!attr) {                                                                                                        \
-                (void)hipFuncSetAttribute((const void*)k_ntt_pass9<CI, CO, TA, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                          128 * 1024);                                                                          \
-                attr = true;                                                                                                    \
-            }                                                                                                                   \
-            hipLaunchKernelGGL((k_ntt_pass9<CI, CO, TA, 512>), grid, dim3(512), lds, st, pp, tab->roots9, s0, K, TL, tab->s,    \
-                               logn, shift9, stage9);                                                                           \
         } else                                                                                                                  \
             hipLaunchKernelGGL((k_ntt_pass9<CI, CO, TA, 256>), grid, dim3(256), lds, st, pp, tab->roots9, s0, K, TL, tab->s,    \
                                logn, shift9, stage9);                                                                           \
@@ -490,15 +454,8 @@ int k16_ntt_enqueue(k16_ctx* ctx, k16::Fr* d_a, uint64_t n, k16_ntt_table* tab, 
     packed9 &= 1;
     if (logn >= 1) {
         if (!skip_bitrev) hipLaunchKernelGGL(k_bitrev, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_a, logn);
-        if (!packed9 && ctx->tune.ntt_unfused) {
-            for (uint32_t s = 1; s <= logn; s++)
-                hipLaunchKernelGGL(k_stage, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, st, d_a, tab->roots, logn,
-                                   s, tab->s);
-        } else {
-            Fr* one[1] = {d_a};
-            const uint32_t pub_tile = ctx->tune.ntt_tile_log ? (uint32_t)std::max(10, std::min(11, ctx->tune.ntt_tile_log)) : 10u;
-            ntt_passes(ctx, one, 1, logn, tab, packed9 != 0, nullptr, nullptr, st, logn >= 12 ? pub_tile : 10u);
-        }
+        Fr* one[1] = {d_a};
+        ntt_passes(ctx, one, 1, logn, tab, packed9 != 0, nullptr, nullptr, st);
     }
     if (inverse && !skip_tail) {
         if (logn == 0) {
@@ -532,9 +489,8 @@ int k16_ntt_coset_chain(k16_ctx* ctx, k16::Fr* const* src, k16::Fr* const* dst, 
         return K16_OK;
     }
     k16_stat_scope ss(ctx, "ntt", st);
-    const uint32_t fwd_tile = ctx->tune.ntt_tile_log ? (uint32_t)std::max(10, std::min(11, ctx->tune.ntt_tile_log)) : 10u;
-    ntt_passes(ctx, src, count, logn, tab, true, dst, shift9, st, logn >= 12 ? fwd_tile : 10u);
-    ntt_passes(ctx, dst, count, logn, tab, true, nullptr, nullptr, st, logn >= 12 ? fwd_tile : 10u);
+    ntt_passes(ctx, src, count, logn, tab, true, dst, shift9, st);
+    ntt_passes(ctx, dst, count, logn, tab, true, nullptr, nullptr, st);
     K16_HIP(ctx, hipGetLastError());
     return K16_OK;
 }

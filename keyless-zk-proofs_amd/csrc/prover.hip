@@ -35,14 +35,6 @@
 #include "bn254_fq9.h"
 #include "spmv_plan.h"
 
-#ifndef K16_CHAIN_PRIO
-// Wave priority of the polynomial chain's kernels.  3 (above everything) until round 6; the witness MSMs' short kernels run at 3
-// too and their accumulations at 0.  With the chain at 1 it still wins against the accumulations it runs beside, but the
-// witness MSMs' fold / weighted-sum tails -- whose end, not the chain's, is what the H accumulation's start waits for -- are no
-// longer held up by NTT waves: p50 over 11 alternating runs on two boxes 5.35-5.57 (median 5.46) against 5.37-5.84 (5.67) ms, equal on
-// a third, two provers unchanged (profiles/r06/ab_wave_priorities.log, ab_chain_priority_second_box.log).  -DK16_CHAIN_PRIO=n to compare.
-#define K16_CHAIN_PRIO 1
-#endif
 using namespace k16;
 
 namespace {
@@ -783,7 +775,7 @@ extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_
         unsigned fc   = 0;
         uint64_t rows = 0;
         k16_msm_fixed_base_info(N, &fc, &rows);
-        if (fc && !ctx->tune.no_fixed_base) {
+        if (fc) {
             K16_HIP_P(ctx, hipMalloc((void**)&p->d_Htab, (size_t)rows * 64), p);
             if ((rc = k16_msm_fixed_base_prepare(ctx, K16_G1, p->d_H, N, p->d_Htab))) {
                 prover_free(p);
@@ -814,7 +806,6 @@ extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_
         // that its kernels are not queued behind the witness MSMs that run beside it
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (ctx->tune.no_stream_priority) greatest = 0;
         K16_HIP_P(ctx, hipStreamCreateWithPriority(&p->st2, hipStreamNonBlocking, greatest), p);
     }
     K16_HIP_P(ctx, hipEventCreateWithFlags(&p->ev_w, hipEventDisableTiming), p);
@@ -869,13 +860,6 @@ extern "C" int k16_prover_create_mem(k16_ctx* ctx, const void* zkey_bytes, size_
         K16_HIP_P(ctx, hipMemcpyAsync(p->d_skip_ac, ac.data(), mb, hipMemcpyHostToDevice, st), p);
         K16_HIP_P(ctx, hipMemcpyAsync(p->d_skip_b, bb.data(), mb, hipMemcpyHostToDevice, st), p);
         K16_HIP_P(ctx, hipStreamSynchronize(st), p);
-        if (ctx->tune.no_skip_zero_rows) {
-            (void)hipFree(p->d_skip_ac);
-            (void)hipFree(p->d_skip_b);
-            p->d_skip_ac = p->d_skip_b = nullptr;
-            p->b_sort    = false;
-            p->b_derive  = false;
-        }
         // scalar classes (msm_classes.hip): tables with equal masks share a list set
         // (Off by default, K16_CLASSES=1: measured on the synthetic Keyless-shape key the two paths execute the same number of
         // VALU instructions per proof -- 2.07 against 2.19 G wave-instructions, the additions of a witness MSM being one per
@@ -989,7 +973,6 @@ extern "C" int k16_prover_create_shared(k16_ctx* ctx, const k16_prover* other, k
     {
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (ctx->tune.no_stream_priority) greatest = 0;
         K16_HIP_P(ctx, hipStreamCreateWithPriority(&p->st2, hipStreamNonBlocking, greatest), p);
     }
     K16_HIP_P(ctx, hipEventCreateWithFlags(&p->ev_w, hipEventDisableTiming), p);
@@ -1174,7 +1157,6 @@ static int prove_guarded(k16_prover* p, const void* h_wtns, uint64_t n_vars, int
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream); // (the witness expansion: it writes the packer's bad-entry flag)
         ctx->forced_c          = 0;
         ctx->parallel_combine  = false;
-        ctx->wait_after_memset = nullptr;
         try {
             if (!err.empty()) ctx->err = err;
         } catch (...) {
@@ -1314,13 +1296,12 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
     K16_HIP(ctx, hipEventRecord(p->ev_w, st));
     K16_HIP(ctx, hipStreamWaitEvent(s2, p->ev_w, 0));
     const unsigned gN = (N + 255) / 256;
-    const bool spmv_n16 = !ctx->tune.spmv_full;
     {
         const uint64_t waves = (uint64_t)p->n_slices + p->n_long;
         if (waves)
             hipLaunchKernelGGL(k_spmv, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s2, p->d_slices, p->n_slices, p->d_rowof,
                                p->d_longs, p->n_long, p->d_wire, p->d_coef, p->d_wtns, p->d_a, p->d_b, N, p->logN,
-                               spmv_n16 ? (const uint16_t*)p->d_n16 : (const uint16_t*)nullptr);
+                               (const uint16_t*)p->d_n16);
     }
     hipLaunchKernelGGL(k_mul, dim3(gN), dim3(256), 0, s2, p->d_c, p->d_a, p->d_b, N); // elementwise: same permutation
     // a, b, c together: iNTT passes in place (input already bit-reversed; the last pass stores [tail, coset shift, bit
@@ -1350,8 +1331,8 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
         ForcedC(k16_ctx* cx, unsigned v) : c(cx), saved(cx->forced_c)
         {
             if (!saved && cx_big(cx, v)) c->forced_c = v;
-            // witness scalars: one bucket holds ~45 % of the points, short segments keep it parallel (K16_WITNESS_SEG: sweep)
-            c->forced_seg = cx->tune.witness_seg ? (unsigned)cx->tune.witness_seg : 32u;
+            // witness scalars: one bucket holds ~45 % of the points, short segments keep it parallel
+            c->forced_seg = 32u;
         }
         static bool cx_big(k16_ctx*, unsigned) { return true; }
         ~ForcedC()
@@ -1371,7 +1352,6 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
     const uint64_t    n_wit = p->n_vars;
 #endif
     unsigned wc = 13;
-    if (ctx->tune.witness_c) wc = (unsigned)ctx->tune.witness_c;
     if (p->n_vars < (1u << 17)) wc = 0; // small circuits: automatic
     // All five MSMs are enqueued back to back; their host tails (conversion + Horner, ~0.3 ms each, ~1.2 ms for
     // G2) run while later MSMs occupy the GPU.
@@ -1393,8 +1373,7 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
             int         lane, group, tab;
             const void* rows;
         } const order[4] = {{0, K16_G1, 0, p->d_A}, {2, K16_G2, 2, p->d_B2}, {1, K16_G1, 3, p->d_C}, {0, K16_G1, 1, p->d_B1}};
-        const bool split = !ctx->tune.no_split_classes;
-        for (int phase = split ? 1 : 0; phase <= (split ? 2 : 0); phase++)
+        for (int phase = 1; phase <= 2; phase++)
             for (int k = 0; k < 4; k++) {
                 ctx->cur_lane = order[k].lane;
                 if (phase != 1 && k > 0) {
@@ -1419,7 +1398,7 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
             ctx->cur_lane  = 2;
             ctx->skip_next = skip_b;
             // (b2_lead: the shared sort contains B's (0,0) rows; B2's accumulation steps over them as it does when it trails)
-            if (b2_lead && !ctx->tune.no_acc_skip && !p->b_derive && p->d_skip_ac) ctx->acc_skip_next = (const uint64_t*)p->d_zmask[2];
+            if (b2_lead && !p->b_derive && p->d_skip_ac) ctx->acc_skip_next = (const uint64_t*)p->d_zmask[2];
             if ((rc = k16_msm_enqueue_prepared(ctx, K16_G2, p->d_B2, p->d_wtns, n_wit))) return rc;
         }
         ctx->cur_lane        = 0;
@@ -1433,8 +1412,7 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
         ctx->skip_next       = skip_ac;
         if ((rc = k16_msm_enqueue_prepared(ctx, K16_G1, p->d_C, p->d_wtns, n_wit))) return rc;
         // B1 / B2 on a sort that contains their (0,0) rows: the accumulation steps over them (k_accumulate_skip)
-        const bool        acc_skip_on = !ctx->tune.no_acc_skip;
-        const bool        b_skip = acc_skip_on && !p->b_sort && !p->b_derive && p->d_skip_ac;
+        const bool        b_skip = !p->b_sort && !p->b_derive && p->d_skip_ac;
         if (p->b_derive && !b2_lead) {
             // B2 first (lane 2): its lists come from lane 0's partition without B's (0,0) rows; B1 (lane 0, after A) reads them
             ctx->cur_lane = 2;
@@ -1443,11 +1421,7 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
             if ((rc = k16_msm_enqueue_prepared(ctx, K16_G2, p->d_B2, p->d_wtns, n_wit))) return rc;
         }
         const bool b_derived = p->b_derive && !b2_lead;
-        // K16_B1_LANE (round 6 experiment): B1 on a lane of its own instead of behind A's MSM on lane 0 -- its accumulation then
-        // starts with A's and C's (they all read lane 0's sort) and its tail runs under the chain, not after it
-        const int b1_lane = (ctx->tune.b1_lane == 3 && ctx->tune.h_lane != 3) ? 3 : 0;
-        if (b1_lane) K16_HIP(ctx, hipStreamWaitEvent(k16_lane_stream(ctx, b1_lane), p->ev_w, 0));
-        ctx->cur_lane        = b1_lane;
+        ctx->cur_lane        = 0; // B1 behind A's MSM
         ctx->reuse_sort      = true;
         ctx->reuse_sort_lane = (p->b_sort || b_derived) ? 2 : own;
         ctx->skip_next       = b_derived ? (const uint64_t*)p->d_skip_b : skip_b;
@@ -1470,15 +1444,9 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
         return K16_ERR_HIP;
     }
     // groth16.cpp:281-283
-    // K16_H_LANE (round 6 experiment): the H MSM on a lane of its own instead of behind C's MSM on lane 1;
-    // K16_H_WAIT_FIRST: its wait for the chain issued behind its sort's memset (msm_sort_launch) instead of here
-    const int   h_lane = ctx->tune.h_lane;
-    hipStream_t sh     = k16_lane_stream(ctx, h_lane);
-    ctx->cur_lane      = h_lane;
-    if (ctx->tune.h_wait_first && p->d_Htab)
-        ctx->wait_after_memset = p->ev_h;
-    else
-        K16_HIP(ctx, hipStreamWaitEvent(sh, p->ev_h, 0));
+    // the H MSM: lane 1, behind C's MSM, once the polynomial chain is done
+    ctx->cur_lane = 1;
+    K16_HIP(ctx, hipStreamWaitEvent(s1, p->ev_h, 0));
     if (p->d_Htab) {
         if (hs_in_sort) {
             ctx->hs_next[0] = p->d_t[0];

@@ -77,6 +77,49 @@ def test_production_library_has_no_result_changing_switches():
     for fn, ln, line in lab_only:
         assert "K16_LAB" in line or "K16_FAULT_INJECT" in line or \
             (fn == "msm_sharded.hip" and ("K16_RCCL_LIB" in line or "K16_RANK_COMM_TIMEOUT_MS" in line)), (fn, ln, line)
+    # ... and WHICH variables the production build reads is a decision, not an accident: a new switch has to be added here
+    assert production_env_names(src) == ENV_ALLOWED
+
+
+# Every "K16_..." name libk16.so passes to getenv (directly or through from_env's one-line helpers).  A name enters this
+# list when a test uses it, a deployer is told about it (INTEGRATION.md / README.md), it is a diagnostic, or the path it
+# forces is live for other inputs; a rejected experiment's switch leaves with its code (DESIGN_HISTORY.md).
+ENV_ALLOWED = {
+    # ctx.hip, k16_tuning::from_env
+    "K16_ATOMIC_SORT", "K16_SEG", "K16_CLASSES", "K16_B_SORT", "K16_B_DERIVE", "K16_B2_FIRST", "K16_FUSED_HSCALARS",
+    "K16_VERIFY_NO_COOP", "K16_VERIFY_COOP_MAX", "K16_VERIFY_COOP_TRACE", "K16_TRACE", "K16_TRACE_ENQ", "K16_TRACE_HOST",
+    "K16_NO_WARMUP",
+    # ctx.hip, the process's host thread pool
+    "K16_HOST_THREADS", "K16_UPLOAD_THREADS",
+    # fullprover.cpp, the facade's constructor
+    "K16_LOG", "K16_DEVICES", "K16_DEVICE", "K16_POOL_STREAM_OFFSET",
+    # msm_sharded.hip, the RCCL leg
+    "K16_RCCL_LIB", "K16_RANK_COMM_TIMEOUT_MS",
+}
+
+
+def production_env_names(src):
+    """The set of "K16_..." string literals that reach getenv in csrc/, outside #ifdef K16_LAB / K16_TESTING blocks: the
+    argument of a getenv( call, or of one of the lambdas of from_env that forward their argument to it."""
+    import re
+    call = re.compile(r'\b(getenv|on|onv|num)\(\s*"(K16_[A-Z0-9_]+)"')
+    names = set()
+    for fn in sorted(os.listdir(src)):
+        if not fn.endswith((".hip", ".inc", ".h", ".cpp")):
+            continue
+        guarded = []                       # one entry per open #if: True when it (or an enclosing one) is a lab / testing block
+        for line in open(os.path.join(src, fn), errors="ignore"):
+            t = line.strip()
+            if t.startswith("#if"):
+                lab = t.startswith("#ifdef") and ("K16_LAB" in t or "K16_TESTING" in t)
+                guarded.append(lab or (bool(guarded) and guarded[-1]))
+            elif t.startswith("#else") and guarded:
+                guarded[-1] = len(guarded) > 1 and guarded[-2]   # the #else of a lab block is production code
+            elif t.startswith("#endif") and guarded:
+                guarded.pop()
+            elif not (guarded and guarded[-1]) and not t.startswith("//"):
+                names.update(m.group(2) for m in call.finditer(line))
+    return names
 
 
 def test_rccl_test_double_is_not_part_of_the_product():
@@ -261,8 +304,8 @@ def test_static_archive_links_and_proves(tmp_path, toy_paths):
 @pytest.mark.gpu
 def test_proofs_through_the_generic_sort_and_its_dropped_masks(tmp_path):
     """the prover always hands its zero-row masks to the bucket sort; on the paths that do not implement a mask
-    (the generic sort every key with more than 2^24 wires takes -- forced here with K16_ATOMIC_SORT -- and the lean
-    variant) the mask is DROPPED, not refused: proofs equal the oracle's."""
+    (the generic sort every key with more than 2^24 wires takes -- forced here with K16_ATOMIC_SORT) the mask is DROPPED,
+    not refused: proofs equal the oracle's."""
     code = '''
 import os, sys
 sys.path[:0] = [%r, %r, %r]
@@ -280,7 +323,7 @@ p.close()
 print("masked proofs OK")
 ''' % (os.path.join(ROOT, "tests"), ROOT, PKG, str(tmp_path / "m.zkey"), str(tmp_path / "m.wtns"), str(tmp_path / "m.zkey"),
        str(tmp_path / "m.zkey"), str(tmp_path / "m.wtns"))
-    for extra in ({"K16_ATOMIC_SORT": "1"}, {"K16_LEAN_SORT": "1"}):
+    for extra in ({"K16_ATOMIC_SORT": "1"},):
         env = dict(os.environ, **extra)
         out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
         assert out.returncode == 0 and "masked proofs OK" in out.stdout, (extra, out.stdout[-1500:] + out.stderr[-3000:])

@@ -43,8 +43,6 @@ tools/lab/prof.sh ${ROUND:-r05}s16 tools/lab/sortlab 20 16 0 uniform 20 > $O/sor
 tools/lab/prof.sh ${ROUND:-r05}sH tools/lab/sortlab 21 20 1 uniform 20 > $O/sortlab_2p21_flat20_kernels.txt 2>&1
 tools/lab/pmc.sh ${ROUND:-r05}w16 WRITE_SIZE tools/lab/sortlab 20 16 0 uniform 3 > $O/sortlab_2p20_c16_WRITE_SIZE.txt 2>&1
 tools/lab/pmc.sh ${ROUND:-r05}wH WRITE_SIZE tools/lab/sortlab 21 20 1 uniform 3 > $O/sortlab_2p21_flat20_WRITE_SIZE.txt 2>&1
-K16_NO_STAGED_SORT=1 tools/lab/sortlab 21 20 1 uniform 20 check > $O/sortlab_2p21_flat20_round3_sort.log 2>&1
-K16_NO_STAGED_SORT=1 tools/lab/sortlab 20 16 0 uniform 20 check > $O/sortlab_2p20_c16_round3_sort.log 2>&1
 # 10a. round 5: instruction costs, gaps between the pipelined accumulations, provers per GPU
 tools/lab/ubench2 > $O/ubench2_instruction_costs.log 2>&1
 rm -rf /tmp/k16_msm_tl; K16_BENCH_NO_COLD=1 rocprofv3 --kernel-trace --output-format csv -d /tmp/k16_msm_tl -- python3 bench.py --full --steps 20 --warmup 5 --proofs 0 --no-cpu-baseline > /dev/null 2> $O/msm_pipeline_gaps.err
