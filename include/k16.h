@@ -466,6 +466,48 @@ int  k16_verify_batch_folded(k16_ctx* ctx, const k16_vk* vk, const void* h_proof
  * fallback; K16_ERR_ARG when a proof fails the point checks or has a zero point, or when MSMs are pending. */
 int  k16_verify_fold_gt(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
                         const void* h_weights, void* h_out_gt);
+/* ---- verified proving: every proof checked on the GPU before it is released (prover_handler.rs:329-336 in one call) ----
+ * The verification key a proving key carries: alpha1, beta2, gamma2, delta2 from section 2 and IC from section 3 of the zkey
+ * (no separate vkey file, no decimal parsing).  Container / curve errors as k16_prover_create_mem; K16_ERR_FORMAT when
+ * section 3 is absent (synthetic keys omit it) or does not hold exactly nPublic + 1 points.  The result is an ordinary k16_vk. */
+int  k16_vk_create_from_zkey(k16_ctx* ctx, const void* zkey, size_t size, k16_vk** out);
+int  k16_vk_create_from_zkey_file(k16_ctx* ctx, const char* zkey_path, k16_vk** out);
+/* Attaches the key the _verified calls check against (NULL detaches; the prover does not own it: destroy it after the
+ * prover, or detach first).  K16_ERR_ARG unless vk belongs to the prover's context and has nPublic + 1 IC points. */
+int  k16_prover_set_vk(k16_prover* p, const k16_vk* vk);
+/* k16_prover_prove_mem / _prove_compact plus the check.  JSON and return value are exactly the plain call's for the same
+ * witness and (r, s).  out_proof (256 B: A | B | C, affine Montgomery LE -- k16_verify_batch's proof format; may be NULL).
+ * *out_ok: the flag k16_verify_batch gives for that proof with the public inputs taken from the witness (rows 1..nPublic of
+ * the mem call's witness; the same wires read from `narrow` or the wide list for the compact call).  A rejected proof is
+ * still written out, with *out_ok = 0 (the witness does not satisfy the circuit): the caller decides.  K16_ERR_ARG when no
+ * key is attached.  On every error path nothing of the call is left in flight.
+ * The check is SPLIT where the prover's data arrive (csrc/verify_script.h): A and B are final while the GPU still works on the
+ * H MSM, so e(A,B) and e(vk_x,-gamma) -- two of the three Miller loops -- run on a stream of the key's own under it; only
+ * e(C,-delta), one Fp12 product and the final exponentiation wait for C.  A case the programs do not decide (a zero point,
+ * vk_x at infinity) is settled by k16_verify_batch after the proof: same flag.  One verified prove at a time per key. */
+int  k16_prover_prove_mem_verified(k16_prover* p, const void* h_wtns, uint64_t n_vars, const uint8_t* r_std, const uint8_t* s_std,
+                                   char* out_json, size_t cap, float* device_ms, uint8_t* out_proof, uint8_t* out_ok);
+int  k16_prover_prove_compact_verified(k16_prover* p, uint64_t n_wide, const uint8_t* r_std, const uint8_t* s_std, char* out_json,
+                                       size_t cap, float* device_ms, uint8_t* out_proof, uint8_t* out_ok);
+/* k16_prover_prove_file_timed with the same check (what FullProver::prove runs once k16_fullprover_set_verify is on) */
+int  k16_prover_prove_file_verified(k16_prover* p, const char* wtns_path, const uint8_t* r_std, const uint8_t* s_std,
+                                    char* out_json, size_t cap, float* device_ms, float* prove_wall_ms, uint8_t* out_proof,
+                                    uint8_t* out_ok);
+/* Verified proving behind the drop-in FullProver (`fullprover` as for k16_fullprover_prove_mem).  on != 0: every pool slot builds
+ * its verification key from the zkey and attaches it (a slot rebuilt after a device fault gets its key again); from then on
+ * FullProver::prove, k16_fullprover_prove_mem and k16_fullprover_prove_compact answer a proof the check rejects with
+ * ProverError::INVALID_INPUT (K16_ERR_FORMAT from the C entry points): the witness does not satisfy the circuit.  on == 0
+ * detaches.  Call it after construction and before the first proof (K16_ERR_ARG while a slot is proving).  K16_ERR_FORMAT: the
+ * zkey has no usable section 3 -- the reason goes to stderr, verification stays off, the provers keep working unverified.
+ * K16_ERR_NO_DEVICE: the object is not ready.  Without the call nothing changes.  (A call, not an environment variable: which
+ * variables the production library reads is a fixed list, tests/test_boundary.py.) */
+int  k16_fullprover_set_verify(const void* fullprover, int on);
+/* parity tests: the split check with no prover involved, n <= 64 proofs: out_early = the multi-Miller value of (A,B) and
+ * (vk_x,-gamma) before any final exponentiation (not canonical: an Fq factor rides on it), out_gt = the GT value, byte-equal
+ * to k16_verify_coop_gt's; n x 12 x 32 B each.  No fallback: K16_ERR_ARG when a proof fails the point checks, has a zero
+ * point, or its vk_x is the point at infinity. */
+int  k16_verify_split_gt(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                         void* h_out_early, void* h_out_gt);
 /* every point of a Groth16 zkey, in the sections that are present: 2 (alpha1, beta1, beta2, gamma2, delta1, delta2 =
  * indices 0..5), 3 (IC; the prover does not need it and synthetic keys omit it), 5 (A), 6 (B1), 7 (B2), 8 (C), 9 (H).
  * K16_OK with *n_bad = 0 when all pass; otherwise the first failure in (section, index) order and the number of failing

@@ -76,21 +76,45 @@ public:
     struct Slot {
         k16_ctx*    ctx    = nullptr;
         k16_prover* prover = nullptr;
+        k16_vk*     vk     = nullptr; // k16_fullprover_set_verify: the slot's verification key, built from the zkey and attached to its prover
         int         device = 0;
         bool        busy   = false;
         bool        dead   = false; // a device fault hit this slot and rebuilding it failed: never handed out again
     };
     std::vector<Slot>       slots;
     std::string             zkey_path; // to rebuild a slot after a device fault
+    // k16_fullprover_set_verify: every proof is checked on the GPU before it is handed out (include/k16.h, verified proving);
+    // a rejected proof -- the witness does not satisfy the circuit -- is answered with INVALID_INPUT / K16_ERR_FORMAT
+    bool                    verify = false;
     std::mutex              mu;
     std::condition_variable cv;
 
     ~FullProverImpl()
     {
-        for (Slot& s : slots) {
-            if (s.prover) k16_prover_destroy(s.prover);
-            if (s.ctx) k16_ctx_destroy(s.ctx);
-        }
+        for (Slot& s : slots) drop(&s);
+    }
+    static void drop(Slot* s)
+    {
+        if (s->prover) k16_prover_destroy(s->prover);
+        if (s->vk) k16_vk_destroy(s->vk);
+        if (s->ctx) k16_ctx_destroy(s->ctx);
+        s->prover = nullptr;
+        s->vk     = nullptr;
+        s->ctx    = nullptr;
+    }
+    // verification on: the slot's key from the zkey's sections 2 and 3, attached to its prover
+    int attach_vk(Slot* s) const
+    {
+        if (!verify || s->vk) return K16_OK;
+        int rc = k16_vk_create_from_zkey_file(s->ctx, zkey_path.c_str(), &s->vk);
+        if (rc == K16_OK) rc = k16_prover_set_vk(s->prover, s->vk);
+        return rc;
+    }
+    static void detach_vk(Slot* s)
+    {
+        if (s->prover) (void)k16_prover_set_vk(s->prover, nullptr);
+        if (s->vk) k16_vk_destroy(s->vk);
+        s->vk = nullptr;
     }
     // blocks until a prover is free; proofs of concurrent callers run on different slots.  nullptr: every slot is dead.
     Slot* acquire()
@@ -117,12 +141,10 @@ public:
     {
         bool ok = false;
         try { // k16_* never throw (their own firewall); this guards the few host statements around them all the same
-            if (s->prover) k16_prover_destroy(s->prover);
-            if (s->ctx) k16_ctx_destroy(s->ctx);
-            s->prover = nullptr;
-            s->ctx    = nullptr;
+            drop(s);
             // (from the key FILE, not from a sibling's resident copy: after a device fault nothing on that device is trusted)
-            ok = k16_ctx_create(s->device, &s->ctx) == K16_OK && k16_prover_create(s->ctx, zkey_path.c_str(), &s->prover) == K16_OK;
+            ok = k16_ctx_create(s->device, &s->ctx) == K16_OK && k16_prover_create(s->ctx, zkey_path.c_str(), &s->prover) == K16_OK &&
+                 attach_vk(s) == K16_OK;
             if (ok) {
                 int sharing = 0;
                 for (auto& o : slots) sharing += o.device == s->device;
@@ -134,10 +156,7 @@ public:
         }
         if (!ok) {
             fprintf(stderr, "k16 FullProver: device %d could not be re-initialised after a fault; slot retired\n", s->device);
-            if (s->prover) k16_prover_destroy(s->prover);
-            if (s->ctx) k16_ctx_destroy(s->ctx);
-            s->prover = nullptr;
-            s->ctx    = nullptr;
+            drop(s);
             std::lock_guard<std::mutex> lk(mu);
             s->dead = true;
         }
@@ -278,11 +297,54 @@ extern "C" int k16_fullprover_prove_mem(const void* fullprover, const void* wtns
             FullProverImpl::Lease lease(fp->impl);
             FullProverImpl::Slot* slot = lease.slot;
             if (!slot) return K16_ERR_NO_DEVICE; // every device of the pool has been retired
-            rc = k16_prover_prove_mem(slot->prover, wtns_values, n_values, nullptr, nullptr, out_json, cap, nullptr);
+            if (fp->impl->verify) {
+                uint8_t ok = 0;
+                rc = k16_prover_prove_mem_verified(slot->prover, wtns_values, n_values, nullptr, nullptr, out_json, cap, nullptr, nullptr, &ok);
+                if (rc >= 0 && !ok) rc = K16_ERR_FORMAT; // rejected by the check: the witness does not satisfy the circuit
+            } else
+                rc = k16_prover_prove_mem(slot->prover, wtns_values, n_values, nullptr, nullptr, out_json, cap, nullptr);
             if (rc == K16_ERR_HIP || rc == K16_ERR_NO_DEVICE) fp->impl->quarantine(slot);
         }
         if (prover_time_ms)
             *prover_time_ms = (int)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return K16_ERR_NOMEM;
+    } catch (...) {
+        return K16_ERR_HIP;
+    }
+}
+
+namespace {
+FullProverImpl* impl_of(const void* fullprover);
+} // namespace
+
+// Verified proving behind the facade (include/k16.h): on = every pool slot builds its verification key from the zkey and
+// attaches it.  All or nothing: when one slot cannot (no section 3 in the zkey), verification stays off.
+extern "C" int k16_fullprover_set_verify(const void* fullprover, int on)
+{
+    try {
+        FullProverImpl* impl = impl_of(fullprover);
+        if (!impl) return K16_ERR_NO_DEVICE;
+        std::lock_guard<std::mutex> lk(impl->mu);
+        for (auto& s : impl->slots)
+            if (s.busy) return K16_ERR_ARG; // a proof in flight: switch before the first prove, or between waves
+        impl->verify = on != 0;
+        int rc = K16_OK;
+        for (auto& s : impl->slots) {
+            if (s.dead) continue;
+            if (!on) FullProverImpl::detach_vk(&s);
+            else if ((rc = impl->attach_vk(&s)) != K16_OK) {
+                fprintf(stderr, "k16 FullProver: no verification key could be built from %s: %s\n", impl->zkey_path.c_str(),
+                        k16_last_error(s.ctx));
+                log_line("ERROR", "verification asked for but the zkey carries no usable verification key");
+                break;
+            }
+        }
+        if (rc != K16_OK) {
+            impl->verify = false;
+            for (auto& s : impl->slots) FullProverImpl::detach_vk(&s);
+        }
         return rc;
     } catch (const std::bad_alloc&) {
         return K16_ERR_NOMEM;
@@ -355,7 +417,13 @@ extern "C" int k16_fullprover_prove_compact(const void* fullprover, void* lease,
         } rel{impl, slot};
         if (!out_json) return K16_ERR_ARG;
         const auto t0 = std::chrono::steady_clock::now();
-        const int  rc = k16_prover_prove_compact(slot->prover, n_wide, nullptr, nullptr, out_json, cap, nullptr);
+        int        rc;
+        if (impl->verify) {
+            uint8_t ok = 0;
+            rc = k16_prover_prove_compact_verified(slot->prover, n_wide, nullptr, nullptr, out_json, cap, nullptr, nullptr, &ok);
+            if (rc >= 0 && !ok) rc = K16_ERR_FORMAT; // rejected by the check: the witness does not satisfy the circuit
+        } else
+            rc = k16_prover_prove_compact(slot->prover, n_wide, nullptr, nullptr, out_json, cap, nullptr);
         if (rc == K16_ERR_HIP || rc == K16_ERR_NO_DEVICE) impl->quarantine(slot);
         if (prover_time_ms)
             *prover_time_ms = (int)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
@@ -395,7 +463,15 @@ ProverResponse FullProver::prove(const char* input) const
             FullProverImpl::Slot* slot = lease.slot;
             if (!slot) return ProverResponse(ProverError::PROVER_NOT_READY); // every device of the pool has been retired
             dev_used = slot->device;
-            rc = k16_prover_prove_file_timed(slot->prover, input, nullptr, nullptr, json, sizeof json, &dev_ms, &prove_ms);
+            if (impl->verify) {
+                uint8_t ok = 0;
+                rc = k16_prover_prove_file_verified(slot->prover, input, nullptr, nullptr, json, sizeof json, &dev_ms, &prove_ms, nullptr, &ok);
+                if (rc >= 0 && !ok) {
+                    log_line("ERROR", "proof rejected by the GPU check: the witness does not satisfy the circuit");
+                    rc = K16_ERR_FORMAT; // -> INVALID_INPUT below
+                }
+            } else
+                rc = k16_prover_prove_file_timed(slot->prover, input, nullptr, nullptr, json, sizeof json, &dev_ms, &prove_ms);
             if (rc < 0 && rc != K16_ERR_CURVE && log_on())
                 fprintf(stderr, "k16 FullProver::prove failed: %s\n", k16_last_error(slot->ctx));
             // A HIP failure is the DEVICE's fault, not the caller's: PROVER_NOT_READY (the service's retry / failover class,

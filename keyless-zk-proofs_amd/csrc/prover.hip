@@ -34,6 +34,7 @@
 #include "points_check.h"
 #include "bn254_fq9.h"
 #include "spmv_plan.h"
+#include "verify_split.h"
 
 using namespace k16;
 
@@ -445,6 +446,7 @@ struct k16_prover {
     void* d_skip_b  = nullptr;
     bool  b_sort    = false;
     bool  b_derive  = false; // B1 / B2 accumulate bucket lists of their own, derived from A's partition without their (0,0) rows
+    const k16_vk* vk = nullptr; // k16_prover_set_vk: what the _verified prove calls check their proofs against (not owned)
 };
 
 // Host side of the compact upload: the context's host threads (k16_ctx_pool) each scan a contiguous range of the witness.
@@ -1122,17 +1124,26 @@ static inline int fault_injected_now() { return 0; }
 int k16_msm_classified_phase(k16_ctx* ctx, int group, const void* d_prepared, const k16_scalar_classes* cls, int set, int phase);
 // prepacked >= 0: the compact hand-off (k16_prover_prove_compact) -- h_wtns is null, the caller has filled the packer's pinned
 // buffers and `prepacked` entries of its wide-value list
+// A verified prove (k16_prover_prove_*_verified): the split check of verify_split.h rides on the proof.  Null for the plain calls,
+// which then execute nothing of it.
+struct VerifyReq {
+    const k16_vk*        vk;
+    std::vector<uint8_t> inputs;           // n_public x 32 B, standard form: wires 1 .. n_public of the witness
+    uint8_t              proof[256] = {0}; // A | B | C, affine Montgomery LE
+    bool                 have_proof = false, decided = false, early_ok = false;
+    uint8_t              ok = 0;
+};
 static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, int64_t prepacked, const uint8_t* r_in,
-                           const uint8_t* s_in, char* out_json, size_t cap, float* device_ms);
+                           const uint8_t* s_in, char* out_json, size_t cap, float* device_ms, VerifyReq* vr);
 
 static int prove_guarded(k16_prover* p, const void* h_wtns, uint64_t n_vars, int64_t prepacked, const uint8_t* r_in,
-                         const uint8_t* s_in, char* out_json, size_t cap, float* device_ms)
+                         const uint8_t* s_in, char* out_json, size_t cap, float* device_ms, VerifyReq* vr = nullptr)
 {
     return k16_guard((p ? p->ctx : nullptr), [&]() -> int {
     if (!p || (!h_wtns && prepacked < 0) || !out_json) return K16_ERR_ARG;
     int rc;
     try {
-        rc = prove_mem_inner(p, h_wtns, n_vars, prepacked, r_in, s_in, out_json, cap, device_ms);
+        rc = prove_mem_inner(p, h_wtns, n_vars, prepacked, r_in, s_in, out_json, cap, device_ms, vr);
     } catch (const std::bad_alloc&) {
         rc = K16_ERR_NOMEM;
         try {
@@ -1214,7 +1225,7 @@ extern "C" int k16_prover_prove_compact(k16_prover* p, uint64_t n_wide, const ui
 }
 
 static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, int64_t prepacked, const uint8_t* r_in,
-                           const uint8_t* s_in, char* out_json, size_t cap, float* device_ms)
+                           const uint8_t* s_in, char* out_json, size_t cap, float* device_ms, VerifyReq* vr)
 {
     k16_ctx* ctx = p->ctx;
     if (n_vars < p->n_vars) { // the reference does not check; reading past the buffer is not an option here
@@ -1510,6 +1521,22 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
     // pi_a and pi_b are final: their affine form and decimal strings are made while the GPU still works on the H MSM
     const G1Aff A = to_affine(pi_a);
     const G2Aff B = to_affine(pi_b);
+    // a verified prove: the check's first two Miller loops need no more than A, B and the public inputs -- on the key's own
+    // stream, under the H MSM.  Whatever finish order led here (b2_first, b2_before_b1, classes), this is the one place where
+    // both are affine.  The session ends (and waits for the key's stream) on every way out of this function.
+    struct SplitSession {
+        const k16_vk* vk = nullptr;
+        ~SplitSession()
+        {
+            if (vk) vk_split_end(vk);
+        }
+    } split;
+    if (vr) {
+        if ((rc = vk_split_begin(vr->vk, vr->inputs.data()))) return rc;
+        split.vk = vr->vk;
+        if ((rc = vk_split_early(vr->vk, A, B)) < 0) return rc;
+        vr->early_ok = rc == K16_OK;
+    }
     const std::string js_ab = "{\"pi_a\":[\"" + fq_to_dec(A.x) + "\",\"" + fq_to_dec(A.y) + "\",\"1\"],\"pi_b\":[[\"" +
                               fq_to_dec(B.x.a) + "\",\"" + fq_to_dec(B.x.b) + "\"],[\"" + fq_to_dec(B.y.a) + "\",\"" +
                               fq_to_dec(B.y.b) + "\"],[\"1\",\"0\"]],\"pi_c\":[\"";
@@ -1547,7 +1574,135 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
     if (js.size() + 1 > cap) return K16_ERR_BUFFER;
     memcpy(out_json, js.c_str(), js.size() + 1);
     ht("proof JSON written");
+    if (vr) { // what had to wait for C: its Miller loop, one Fp12 product, the final exponentiation
+        memcpy(vr->proof, &A, 64);
+        memcpy(vr->proof + 64, &B, 128);
+        memcpy(vr->proof + 192, &Cc, 64);
+        vr->have_proof = true;
+        rc             = vr->early_ok ? vk_split_late(vr->vk, Cc, &vr->ok) : K16_SPLIT_UNDECIDED;
+        if (rc < 0) return rc;
+        vr->decided = rc == K16_OK;
+        ht("proof verified");
+    }
     return (int)js.size();
+}
+
+// ---- verified proving (include/k16.h): the proof is checked against the attached key before the call returns
+extern "C" int k16_prover_set_vk(k16_prover* p, const k16_vk* vk)
+{
+    if (!p) return K16_ERR_ARG;
+    if (vk && (vk_split_ctx(vk) != p->ctx || vk_split_n_ic(vk) != p->n_public + 1)) {
+        try {
+            p->ctx->err = vk_split_ctx(vk) != p->ctx ? "k16_prover_set_vk: the key belongs to another context"
+                                                      : "k16_prover_set_vk: the key's IC count is not the circuit's nPublic + 1";
+        } catch (...) {
+        }
+        return K16_ERR_ARG;
+    }
+    p->vk = vk;
+    return K16_OK;
+}
+
+static int prove_verified(k16_prover* p, const void* h_wtns, uint64_t n_vars, int64_t prepacked, const uint8_t* r_in,
+                          const uint8_t* s_in, char* out_json, size_t cap, float* device_ms, uint8_t* out_proof, uint8_t* out_ok)
+{
+    if (!p || !out_ok) return K16_ERR_ARG;
+    if (!p->vk) {
+        try {
+            p->ctx->err = "verified prove: no verification key attached (k16_prover_set_vk)";
+        } catch (...) {
+        }
+        return K16_ERR_ARG;
+    }
+    *out_ok = 0;
+    VerifyReq vr;
+    vr.vk = p->vk;
+    int rc = k16_guard(p->ctx, [&]() -> int {
+        // the public inputs: wires 1 .. n_public, 32 B standard form each
+        const uint32_t np = p->n_public;
+        vr.inputs.assign((size_t)np * 32 + 1, 0);
+        if (prepacked < 0) {
+            if (n_vars >= p->n_vars) memcpy(vr.inputs.data(), (const uint8_t*)h_wtns + 32, (size_t)np * 32); // (too short: the prove reports it)
+        } else {
+            const WitnessPacker* w = p->packer;
+            for (uint32_t j = 1; j <= np; j++) vr.inputs[(size_t)(j - 1) * 32] = w->h_narrow[j];
+            for (int64_t k = 0; k < prepacked; k++) { // a wide public input: its narrow byte is 0, its value is in the list
+                const uint32_t wire = w->h_idx[k];
+                if (wire >= 1 && wire <= np) memcpy(&vr.inputs[(size_t)(wire - 1) * 32], w->h_val + (size_t)k * 32, 32);
+            }
+        }
+        return K16_OK;
+    });
+    if (rc) return rc;
+    rc = prove_guarded(p, h_wtns, n_vars, prepacked, r_in, s_in, out_json, cap, device_ms, &vr);
+    if (rc < 0) return rc;
+    if (!vr.decided) { // a zero point, vk_x at infinity, a key without the split programs: rare, and the same flag
+        const int r2 = k16_verify_batch(p->ctx, vr.vk, vr.proof, vr.inputs.data(), 1, &vr.ok);
+        if (r2) return r2;
+    }
+    if (out_proof) memcpy(out_proof, vr.proof, 256);
+    *out_ok = vr.ok;
+    return rc;
+}
+
+extern "C" int k16_prover_prove_mem_verified(k16_prover* p, const void* h_wtns, uint64_t n_vars, const uint8_t* r_in,
+                                             const uint8_t* s_in, char* out_json, size_t cap, float* device_ms, uint8_t* out_proof,
+                                             uint8_t* out_ok)
+{
+    if (!h_wtns) return K16_ERR_ARG;
+    return prove_verified(p, h_wtns, n_vars, -1, r_in, s_in, out_json, cap, device_ms, out_proof, out_ok);
+}
+
+extern "C" int k16_prover_prove_compact_verified(k16_prover* p, uint64_t n_wide, const uint8_t* r_in, const uint8_t* s_in,
+                                                 char* out_json, size_t cap, float* device_ms, uint8_t* out_proof, uint8_t* out_ok)
+{
+    if (!p || !out_json) return K16_ERR_ARG;
+    WitnessPacker* w = p->packer;
+    if (!w || n_wide > (uint64_t)w->n_threads * w->cap) {
+        try {
+            p->ctx->err = w ? "compact hand-off: more wide values than the list holds (use k16_prover_prove_mem_verified)"
+                            : "compact hand-off: this prover uploads its witness plainly";
+        } catch (...) {
+        }
+        return K16_ERR_ARG;
+    }
+    return prove_verified(p, nullptr, p->n_vars, (int64_t)n_wide, r_in, s_in, out_json, cap, device_ms, out_proof, out_ok);
+}
+
+// The verification key a proving key carries: alpha1, beta2, gamma2, delta2 in section 2, IC in section 3.  Container and
+// curve checks are the prover's (zkey_header).
+extern "C" int k16_vk_create_from_zkey(k16_ctx* ctx, const void* zkey, size_t size, k16_vk** out)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !zkey || !out) return K16_ERR_ARG;
+    *out = nullptr;
+    BinView    bv;
+    ZkeyHeader zh;
+    int        rc = zkey_header(ctx, (const uint8_t*)zkey, size, &bv, &zh);
+    if (rc) return rc;
+    const uint64_t n_ic = (uint64_t)zh.n_public + 1;
+    if (!bv.sec[3].p || bv.sec[3].size != n_ic * 64) {
+        ctx->err = bv.sec[3].p ? "zkey: section 3 does not hold exactly nPublic + 1 points" : "zkey: no section 3 (IC): no verification key in this file";
+        return K16_ERR_FORMAT;
+    }
+    const uint8_t* h = zh.pts; // alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2
+    return k16_vk_create(ctx, h, h + 128, h + 256, h + 448, bv.sec[3].p, (uint32_t)n_ic, out);
+    });
+}
+
+extern "C" int k16_vk_create_from_zkey_file(k16_ctx* ctx, const char* zkey_path, k16_vk** out)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !zkey_path || !out) return K16_ERR_ARG;
+    *out = nullptr;
+    MappedFile mf;
+    int        rc = mf.open_ro(zkey_path);
+    if (rc) {
+        ctx->err = std::string("zkey: cannot open/map ") + zkey_path;
+        return rc;
+    }
+    return k16_vk_create_from_zkey(ctx, mf.base, mf.size, out);
+    });
 }
 
 extern "C" int k16_prover_prove_file(k16_prover* p, const char* wtns_path, const uint8_t* r_std, const uint8_t* s_std,
@@ -1558,8 +1713,26 @@ extern "C" int k16_prover_prove_file(k16_prover* p, const char* wtns_path, const
 
 // prove_wall_ms: host wall time of the proof itself, i.e. what RS/fullprover.cpp:226-231 brackets (`prover->prove(...)`,
 // after the witness file has been opened, mapped and its header checked at :205-221)
+static int prove_file_inner(k16_prover* p, const char* wtns_path, const uint8_t* r_std, const uint8_t* s_std, char* out_json,
+                            size_t cap, float* device_ms, float* prove_wall_ms, bool verified, uint8_t* out_proof, uint8_t* out_ok);
+
 extern "C" int k16_prover_prove_file_timed(k16_prover* p, const char* wtns_path, const uint8_t* r_std, const uint8_t* s_std,
                                            char* out_json, size_t cap, float* device_ms, float* prove_wall_ms)
+{
+    return prove_file_inner(p, wtns_path, r_std, s_std, out_json, cap, device_ms, prove_wall_ms, false, nullptr, nullptr);
+}
+
+// k16_prover_prove_file_timed with the check of k16_prover_prove_mem_verified (the drop-in FullProver with k16_fullprover_set_verify on)
+extern "C" int k16_prover_prove_file_verified(k16_prover* p, const char* wtns_path, const uint8_t* r_std, const uint8_t* s_std,
+                                              char* out_json, size_t cap, float* device_ms, float* prove_wall_ms, uint8_t* out_proof,
+                                              uint8_t* out_ok)
+{
+    if (!out_ok) return K16_ERR_ARG;
+    return prove_file_inner(p, wtns_path, r_std, s_std, out_json, cap, device_ms, prove_wall_ms, true, out_proof, out_ok);
+}
+
+static int prove_file_inner(k16_prover* p, const char* wtns_path, const uint8_t* r_std, const uint8_t* s_std, char* out_json,
+                            size_t cap, float* device_ms, float* prove_wall_ms, bool verified, uint8_t* out_proof, uint8_t* out_ok)
 {
     return k16_guard((p ? p->ctx : nullptr), [&]() -> int {
     if (prove_wall_ms) *prove_wall_ms = 0.f;
@@ -1588,7 +1761,8 @@ extern "C" int k16_prover_prove_file_timed(k16_prover* p, const char* wtns_path,
     // section's own length says how many values there are, and prove_mem checks that against the circuit)
     uint64_t have = bv.sec[2].size / 32;
     const auto t0 = std::chrono::steady_clock::now();
-    rc            = k16_prover_prove_mem(p, bv.sec[2].p, have, r_std, s_std, out_json, cap, device_ms);
+    rc            = verified ? k16_prover_prove_mem_verified(p, bv.sec[2].p, have, r_std, s_std, out_json, cap, device_ms, out_proof, out_ok)
+                             : k16_prover_prove_mem(p, bv.sec[2].p, have, r_std, s_std, out_json, cap, device_ms);
     if (prove_wall_ms) *prove_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
     });

@@ -19,6 +19,7 @@
 #include "verify_script.h"
 #include "bn254_points.h"
 #include "points_check.h"
+#include "verify_split.h"
 
 using namespace k16;
 
@@ -54,6 +55,20 @@ struct k16_vk {
     uint32_t *          d_fe_terms = nullptr, *d_fe_hdr = nullptr, *d_fe_chunks = nullptr;
     uint32_t            fe_n_chunks = 0, fe_chunk_words = 0, fe_lds_bytes = 0;
     bool                fold = false;
+    // the split check (k16_prover_prove_*_verified, k16_verify_split_gt): the early [0] and the late [1] program on the
+    // device, the early Miller values (device memory, SMALL_N x 12 Fq) and -- created at first use -- a stream of the key's
+    // own and a pinned device-mapped buffer: SMALL_N proofs | their public inputs | their status bytes
+    struct SplitProg {
+        uint64_t* d_words = nullptr;
+        uint32_t *d_terms = nullptr, *d_hdr = nullptr, *d_chunks = nullptr;
+        uint32_t  n_chunks = 0, chunk_words = 0, lds_bytes = 0;
+    } sp[2];
+    bool                split   = false;
+    Fq*                 d_early = nullptr;
+    mutable std::mutex  split_mu;
+    mutable hipStream_t split_stream = nullptr;
+    mutable uint8_t *   h_split = nullptr, *d_split = nullptr;
+    mutable bool        split_early_launched = false; // (a verified prove in progress, under split_mu)
 };
 
 namespace {
@@ -175,7 +190,12 @@ __device__ __forceinline__ T coop_shfl_down(const T& v, unsigned delta)
 // FOLD (k16_verify_batch_folded): the same interpreter behind a short prologue -- no point checks, no vk_x: `proofs` holds
 // the program's inputs, 12 canonical Fq per block (an Fp12 value), `ctab9` the constants the program names, and the
 // program is coop_build_finalexp_program's.  The per-proof instantiations compile none of it.
-template <bool DBG, bool FOLD = false>
+// EARLY / LATE (the split check of k16_prover_prove_*_verified, programs coop_build_early_program / coop_build_late_program):
+//   EARLY  point checks of A and B, vk_x, the program; its 12 values go to gt_out (device memory), status 1 = "so far so good"
+//   LATE   runs only where status is 1; point check of C; `inputs` holds the early values (12 canonical Fq per proof); the
+//          program's value is compared with e(alpha, beta) as in the single program
+enum : int { COOP_FULL = 0, COOP_FOLD = 1, COOP_EARLY = 2, COOP_LATE = 3 };
+template <bool DBG, int MODE = COOP_FULL>
 __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* __restrict__ ctab9, const G1Aff* __restrict__ wtab,
                                                     const G1Aff* __restrict__ ic, uint32_t n_ic,
                                                     const uint8_t* __restrict__ proofs, const uint8_t* __restrict__ inputs,
@@ -183,6 +203,7 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
                                                     Fq* __restrict__ gt_out, uint64_t* __restrict__ dbg_ptr,
                                                     const Fq2* __restrict__ twist_b)
 {
+    constexpr bool  FOLD = MODE == COOP_FOLD;
     uint64_t* const dbg = DBG ? dbg_ptr : nullptr; // (compile-time null in the production instantiation: no timing code)
     // dbg (K16_VERIFY_COOP_TRACE=1, proof 0 only): 100 MHz time stamps -- start, constants copied, vk_x done, inputs stored,
     // program done -- then the ticks spent staging chunks and in multiply / linear / inversion steps
@@ -232,9 +253,11 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
     } else
     if (!loader) {
     // ---- input validation (canonical coordinates, on the curve / the twist): an invalid proof is rejected here
-    {
+    if constexpr (MODE == COOP_LATE)
+        if (status[pi] != 1) undecided = 4; // settled (or left undecided) by the early kernel: nothing to do, status stays
+    if (undecided == 0) {
         bool ok_in = true;
-        if (lane == 0 || lane == 1) {
+        if ((lane == 0 && MODE != COOP_LATE) || (lane == 1 && MODE != COOP_EARLY)) {
             G1Aff a;
             const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + pi * 256 + (lane == 0 ? 0 : 192));
 #pragma unroll
@@ -243,7 +266,7 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
                 a.y.v[k] = src[8 + k];
             }
             ok_in = g1_input_ok(a);
-        } else if (lane == 2) {
+        } else if (lane == 2 && MODE != COOP_LATE) {
             G2Aff b;
             const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + pi * 256 + 64);
 #pragma unroll
@@ -267,6 +290,8 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
     // ---- vk_x = IC[0] + sum_j x_j IC[j+1] (ark-groth16 prepare_inputs): one table row per (input, 4-bit window), a lane
     // per window, then a shuffle tree.  x_j acts as a 256-bit integer (G1 has order r), as in the general path.
     stamp(1);
+    Fq       vk_s[3] = {Fq::zero(), Fq::zero(), Fq::zero()}; // X ZZZ, Y ZZ, ZZ ZZZ: vk_x stays projective (verify_script.h)
+    if constexpr (MODE != COOP_LATE) {
     G1Xyzz acc = G1Xyzz::zero();
     for (uint32_t idx = lane; idx < (n_ic - 1) * 64; idx += 64) {
         const uint32_t j = idx >> 6, w = idx & 63;
@@ -279,7 +304,6 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
         G1Xyzz o = coop_shfl_down(acc, d); // (lanes >= 64 - d read their own value: their sums are not used)
         acc      = padd(acc, o);
     }
-    Fq       vk_s[3] = {Fq::zero(), Fq::zero(), Fq::zero()}; // X ZZZ, Y ZZ, ZZ ZZZ: vk_x stays projective (verify_script.h)
     if (lane == 0) {
         acc = padd_mixed(acc, ic[0]);
         if (acc.is_zero()) {
@@ -292,25 +316,38 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
     }
     undecided = (uint32_t)__shfl((int)undecided, 0, 64);
     if (undecided && lane == 0) status[pi] = 2;
+    } // vk_x
     if (!undecided) {
     stamp(2);
     // ---- inputs -> slots: A.x A.y | B.x.a B.x.b B.y.a B.y.b | C.x C.y | vk_x as (X ZZZ, Y ZZ, ZZ ZZZ)
+    // (EARLY: the same without C; LATE: the 12 early values | C.x C.y)
     {
+        constexpr uint32_t n_pr = MODE == COOP_EARLY ? 6 : 8; // coordinates taken from the proof, A.x first
+        constexpr uint32_t n_in = MODE == COOP_EARLY ? COOP_EARLY_INPUTS : MODE == COOP_LATE ? COOP_LATE_INPUTS : COOP_N_INPUTS;
         Fq v = Fq::zero();
-        if (lane < 8) {
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + pi * 256 + lane * 32);
+        if constexpr (MODE == COOP_LATE) {
+            if (lane < n_in) {
+                const uint32_t* src = reinterpret_cast<const uint32_t*>(lane < 12 ? inputs + (pi * 12 + lane) * 32
+                                                                                  : proofs + pi * 256 + 192 + (lane - 12) * 32);
 #pragma unroll
-            for (int k = 0; k < 8; k++) v.v[k] = src[k];
-        }
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const uint32_t x = (uint32_t)__shfl((int)vk_s[j].v[k], 0, 64);
-                if (lane == 8 + j) v.v[k] = x;
+                for (int k = 0; k < 8; k++) v.v[k] = src[k];
             }
+        } else {
+            if (lane < n_pr) {
+                const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + pi * 256 + lane * 32);
+#pragma unroll
+                for (int k = 0; k < 8; k++) v.v[k] = src[k];
+            }
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const uint32_t x = (uint32_t)__shfl((int)vk_s[j].v[k], 0, 64);
+                    if (lane == n_pr + j) v.v[k] = x;
+                }
+        }
         const Fq9 v9 = fq9_from_fq(v);
-        if (lane < COOP_N_INPUTS) coop_st9(slots, D.in_base + lane, v9);
+        if (lane < n_in) coop_st9(slots, D.in_base + lane, v9);
     }
     } // !undecided
     } // input valid
@@ -477,6 +514,11 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
     stamp(4);
     if (dbg && blockIdx.x == 0 && threadIdx.x == 0)
         for (int k = 0; k < 4; k++) dbg[5 + k] = tk[k];
+    if constexpr (MODE == COOP_EARLY) { // the Miller value of the two pairs, canonical, for the late kernel
+        if (lane < 12) gt_out[pi * 12 + lane] = fq9_to_fq(coop_ld9(slots, D.out_slot[lane]));
+        if (lane == 0) status[pi] = 1;
+        return;
+    }
     // ---- the GT value, canonical, against e(alpha, beta)
     bool same = true;
     if (lane < 12) {
@@ -583,6 +625,27 @@ const CoopProgram* fold_program()
     return prog;
 }
 
+// the split check's programs: [0] early, [1] late
+const CoopProgram* split_program(int which)
+{
+    static std::once_flag once;
+    static CoopProgram*   prog[2] = {nullptr, nullptr};
+    std::call_once(once, []() {
+        try {
+            PairConsts K;
+            pairing_consts_init(&K);
+            CoopProgram *e = new CoopProgram(), *l = new CoopProgram();
+            coop_build_early_program(K, e);
+            coop_build_late_program(K, l);
+            prog[0] = e;
+            prog[1] = l;
+        } catch (...) {
+            prog[0] = prog[1] = nullptr;
+        }
+    });
+    return prog[which];
+}
+
 struct DevBufs {
     std::vector<void*> p;
     ~DevBufs()
@@ -618,11 +681,17 @@ extern "C" void k16_vk_destroy(k16_vk* vk)
     if (vk->ctx) (void)hipSetDevice(vk->ctx->device);
     void* bufs[] = {vk->d_ic, vk->d_g2, vk->d_K, vk->d_eab, vk->d_words, vk->d_terms, vk->d_hdr, vk->d_chunks, vk->d_ctab9,
                     vk->d_wtab, vk->d_target, vk->d_small_pr, vk->d_small_in, vk->d_small_st, vk->d_fe_words, vk->d_fe_terms,
-                    vk->d_fe_hdr, vk->d_fe_chunks};
+                    vk->d_fe_hdr, vk->d_fe_chunks, vk->d_early, vk->sp[0].d_words, vk->sp[0].d_terms, vk->sp[0].d_hdr,
+                    vk->sp[0].d_chunks, vk->sp[1].d_words, vk->sp[1].d_terms, vk->sp[1].d_hdr, vk->sp[1].d_chunks};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (vk->chk_stream) (void)hipStreamDestroy(vk->chk_stream);
     if (vk->h_chk) (void)hipHostFree(vk->h_chk);
+    if (vk->split_stream) {
+        (void)hipStreamSynchronize(vk->split_stream);
+        (void)hipStreamDestroy(vk->split_stream);
+    }
+    if (vk->h_split) (void)hipHostFree(vk->h_split);
     delete vk;
     });
 }
@@ -758,9 +827,33 @@ extern "C" int k16_vk_create(k16_ctx* ctx, const void* alpha1, const void* beta2
                            up((void**)&vk->d_fe_terms, F->terms.data(), F->terms.size() * 4) &&
                            up((void**)&vk->d_fe_hdr, fl.hdr.data(), fl.hdr.size() * 4) &&
                            up((void**)&vk->d_fe_chunks, fl.chunks.data(), fl.chunks.size() * 4) &&
-                           hipFuncSetAttribute((const void*)k_verify_coop<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                           hipFuncSetAttribute((const void*)k_verify_coop<false, COOP_FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)vk->fe_lds_bytes) == hipSuccess;
                 if (!vk->fold) (void)hipGetLastError();
+            }
+            // the split check: the early and the late program, same interpreter, same constant table
+            if (vk->coop && split_program(0)) {
+                bool ok = true;
+                for (int w = 0; w < 2 && ok; w++) {
+                    const CoopProgram* S = split_program(w);
+                    CoopLayout         sl;
+                    coop_layout(S, &sl);
+                    k16_vk::SplitProg& sp = vk->sp[w];
+                    sp.n_chunks    = sl.n_chunks;
+                    sp.chunk_words = sl.chunk_words;
+                    sp.lds_bytes   = sl.lds_bytes;
+                    ok = S->n_const == P->n_const && sp.lds_bytes + static_lds <= 160 * 1024 &&
+                         up((void**)&sp.d_words, S->words.data(), S->words.size() * 8) &&
+                         up((void**)&sp.d_terms, S->terms.data(), S->terms.size() * 4) &&
+                         up((void**)&sp.d_hdr, sl.hdr.data(), sl.hdr.size() * 4) &&
+                         up((void**)&sp.d_chunks, sl.chunks.data(), sl.chunks.size() * 4);
+                }
+                vk->split = ok && hipMalloc((void**)&vk->d_early, k16_vk::SMALL_N * 12 * sizeof(Fq)) == hipSuccess &&
+                            hipFuncSetAttribute((const void*)k_verify_coop<false, COOP_EARLY>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)vk->sp[0].lds_bytes) == hipSuccess &&
+                            hipFuncSetAttribute((const void*)k_verify_coop<false, COOP_LATE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)vk->sp[1].lds_bytes) == hipSuccess;
+                if (!vk->split) (void)hipGetLastError();
             }
         }
     }
@@ -852,6 +945,166 @@ static int verify_coop(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, con
         if (stt[i] > 1) return 1;
     if (h_ok) memcpy(h_ok, stt.data(), n);
     return K16_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the split check
+namespace {
+constexpr size_t SPLIT_IN_OFF = k16_vk::SMALL_N * 256;
+size_t split_st_off(const k16_vk* vk) { return SPLIT_IN_OFF + k16_vk::SMALL_N * (size_t)(vk->n_ic - 1) * 32; }
+
+// the key's stream and mapped buffer, under split_mu
+int split_resources(k16_ctx* ctx, const k16_vk* vk)
+{
+    if (!vk->split_stream) K16_HIP(ctx, hipStreamCreateWithFlags(&vk->split_stream, hipStreamNonBlocking));
+    if (!vk->h_split) {
+        K16_HIP(ctx, hipHostMalloc((void**)&vk->h_split, split_st_off(vk) + k16_vk::SMALL_N, hipHostMallocMapped | hipHostMallocCoherent));
+        K16_HIP(ctx, hipHostGetDevicePointer((void**)&vk->d_split, vk->h_split, 0));
+    }
+    return K16_OK;
+}
+
+// launches the early (which = 0) or the late (1) kernel for the n proofs the mapped buffer holds
+int split_launch(k16_ctx* ctx, const k16_vk* vk, int which, uint64_t n, Fq* d_gt)
+{
+    const CoopProgram*       S  = split_program(which);
+    const k16_vk::SplitProg& sp = vk->sp[which];
+    CoopDev                  D;
+    D.words = sp.d_words;
+    D.terms = sp.d_terms;
+    D.hdr = sp.d_hdr;
+    D.chunks = sp.d_chunks;
+    D.n_chunks = sp.n_chunks;
+    D.chunk_words = sp.chunk_words;
+    D.n_const = S->n_const;
+    D.in_base = S->in_base;
+    D.n_slots = S->n_slots;
+    D.target_const = S->target_const;
+    for (int i = 0; i < 12; i++) D.out_slot[i] = S->out_slot[i];
+    const uint8_t* d_pr = vk->d_split;
+    uint8_t*       d_st = vk->d_split + split_st_off(vk);
+    if (which == 0)
+        hipLaunchKernelGGL((k_verify_coop<false, COOP_EARLY>), dim3((unsigned)n), dim3(128), sp.lds_bytes, vk->split_stream, D, vk->d_ctab9,
+                           vk->d_wtab, vk->d_ic, vk->n_ic, d_pr, (const uint8_t*)(vk->d_split + SPLIT_IN_OFF), vk->d_target, d_st, vk->d_early,
+                           (uint64_t*)nullptr, &vk->d_K->twist_b);
+    else
+        hipLaunchKernelGGL((k_verify_coop<false, COOP_LATE>), dim3((unsigned)n), dim3(128), sp.lds_bytes, vk->split_stream, D, vk->d_ctab9,
+                           vk->d_wtab, vk->d_ic, vk->n_ic, d_pr, reinterpret_cast<const uint8_t*>(vk->d_early), vk->d_target, d_st, d_gt,
+                           (uint64_t*)nullptr, &vk->d_K->twist_b);
+    K16_HIP(ctx, hipGetLastError());
+    return K16_OK;
+}
+bool all_zero(const void* p, size_t len)
+{
+    const uint8_t* b = (const uint8_t*)p;
+    for (size_t k = 0; k < len; k++)
+        if (b[k]) return false;
+    return true;
+}
+} // namespace
+
+namespace k16 {
+k16_ctx* vk_split_ctx(const k16_vk* vk) { return vk->ctx; }
+uint32_t vk_split_n_ic(const k16_vk* vk) { return vk->n_ic; }
+int vk_split_begin(const k16_vk* vk, const uint8_t* inputs)
+{
+    vk->split_mu.lock();
+    vk->split_early_launched = false;
+    if (!vk->split) return K16_OK; // (early / late then answer K16_SPLIT_UNDECIDED)
+    int rc = split_resources(vk->ctx, vk);
+    if (rc) {
+        vk->split_mu.unlock();
+        return rc;
+    }
+    if (vk->n_ic > 1) memcpy(vk->h_split + SPLIT_IN_OFF, inputs, (size_t)(vk->n_ic - 1) * 32);
+    return K16_OK;
+}
+int vk_split_early(const k16_vk* vk, const G1Aff& A, const G2Aff& B)
+{
+    if (!vk->split || all_zero(&A, sizeof A) || all_zero(&B, sizeof B)) return K16_SPLIT_UNDECIDED;
+    memcpy(vk->h_split, &A, 64);
+    memcpy(vk->h_split + 64, &B, 128);
+    vk->h_split[split_st_off(vk)] = 2;
+    int rc = split_launch(vk->ctx, vk, 0, 1, nullptr);
+    if (rc == K16_OK) vk->split_early_launched = true;
+    return rc;
+}
+int vk_split_late(const k16_vk* vk, const G1Aff& C, uint8_t* out_ok)
+{
+    if (!vk->split_early_launched || all_zero(&C, sizeof C)) return K16_SPLIT_UNDECIDED;
+    memcpy(vk->h_split + 192, &C, 64);
+    int rc = split_launch(vk->ctx, vk, 1, 1, nullptr);
+    if (rc) return rc;
+    K16_HIP(vk->ctx, hipStreamSynchronize(vk->split_stream));
+    vk->split_early_launched = false;
+    const uint8_t st = vk->h_split[split_st_off(vk)];
+    if (st > 1) return K16_SPLIT_UNDECIDED;
+    *out_ok = st;
+    return K16_OK;
+}
+void vk_split_end(const k16_vk* vk)
+{
+    if (vk->split_early_launched && vk->split_stream) (void)hipStreamSynchronize(vk->split_stream);
+    vk->split_early_launched = false;
+    vk->split_mu.unlock();
+}
+} // namespace k16
+
+// parity tests: the split check with no prover involved -- early then late for n <= 64 proofs.  out_early: the raw multi-Miller
+// value of (A, B), (vk_x, -gamma) per proof (NOT canonical: an Fq factor rides on it until the final exponentiation);
+// out_gt: the GT value, byte-equal to k16_verify_coop_gt's.  12 x 32 B each.  No fallback: K16_ERR_ARG when a proof fails the
+// point checks, has a zero point, or its vk_x is the point at infinity, and when the key has no split programs.
+extern "C" int k16_verify_split_gt(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h_inputs, uint64_t n,
+                                   void* h_out_early, void* h_out_gt)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !vk || vk->ctx != ctx || !n || n > k16_vk::SMALL_N || !h_proofs || !h_out_early || !h_out_gt ||
+        (vk->n_ic > 1 && !h_inputs))
+        return K16_ERR_ARG;
+    if (!vk->split) {
+        ctx->err = "k16_verify_split_gt: the split programs are not available for this key";
+        return K16_ERR_ARG;
+    }
+    const G2Consts& G = g2_consts_host();
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t* pr = (const uint8_t*)h_proofs + i * 256;
+        G1Aff          a, c;
+        G2Aff          b;
+        memcpy(&a, pr, 64);
+        memcpy(&b, pr + 64, 128);
+        memcpy(&c, pr + 192, 64);
+        const bool zero = all_zero(&a, 64) || all_zero(&b, 128) || all_zero(&c, 64);
+        if (zero || !g1_input_ok(a) || !g1_input_ok(c) || !g2_input_ok(b, G.twist_b)) {
+            ctx->err = "k16_verify_split_gt: proof " + std::to_string(i) + (zero ? " has a zero point" : " fails the point checks");
+            return K16_ERR_ARG;
+        }
+    }
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> lock(vk->split_mu);
+    int rc = split_resources(ctx, vk);
+    if (rc) return rc;
+    DevBufs tmp;
+    Fq*     d_gt = nullptr;
+    K16_HIP(ctx, tmp.alloc((void**)&d_gt, (size_t)n * 12 * sizeof(Fq)));
+    memcpy(vk->h_split, h_proofs, (size_t)n * 256);
+    if (vk->n_ic > 1) memcpy(vk->h_split + SPLIT_IN_OFF, h_inputs, (size_t)n * (vk->n_ic - 1) * 32);
+    memset(vk->h_split + split_st_off(vk), 2, n);
+    hipStream_t st = vk->split_stream;
+    rc = split_launch(ctx, vk, 0, n, nullptr);
+    if (!rc) rc = split_launch(ctx, vk, 1, n, d_gt);
+    hipError_t e = hipSuccess;
+    if (!rc && (e = hipMemcpyAsync(h_out_early, vk->d_early, (size_t)n * 12 * sizeof(Fq), hipMemcpyDeviceToHost, st)) == hipSuccess)
+        e = hipMemcpyAsync(h_out_gt, d_gt, (size_t)n * 12 * sizeof(Fq), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st); // d_gt belongs to this call: wait whatever happened
+    if (rc) return rc;
+    K16_HIP(ctx, e);
+    K16_HIP(ctx, es);
+    for (uint64_t i = 0; i < n; i++)
+        if (vk->h_split[split_st_off(vk) + i] > 1) {
+            ctx->err = "k16_verify_split_gt: vk_x of proof " + std::to_string(i) + " is the point at infinity";
+            return K16_ERR_ARG;
+        }
+    return K16_OK;
+    });
 }
 
 // parity tests: the GT value e(A,B) e(vk_x,-gamma) e(C,-delta) of every proof as the wave-cooperative path computes it
@@ -1309,7 +1562,7 @@ int fold_run(k16_ctx* ctx, const k16_vk* vk, const void* h_proofs, const void* h
         for (int i = 0; i < 12; i++) D.out_slot[i] = F->out_slot[i];
         k16_stat_scope sc(ctx, "fold_finalexp");
         // (status and target are the per-proof kernel's: the flag it writes, into this call's d_re, is not read -- V is compared on the host)
-        hipLaunchKernelGGL((k_verify_coop<false, true>), dim3(1), dim3(128), vk->fe_lds_bytes, st, D, vk->d_ctab9, (const G1Aff*)nullptr,
+        hipLaunchKernelGGL((k_verify_coop<false, COOP_FOLD>), dim3(1), dim3(128), vk->fe_lds_bytes, st, D, vk->d_ctab9, (const G1Aff*)nullptr,
                            (const G1Aff*)nullptr, 0u, reinterpret_cast<const uint8_t*>(d_val), (const uint8_t*)nullptr, vk->d_target, d_re,
                            d_gt, (uint64_t*)nullptr, (const Fq2*)nullptr);
         K16_HIP(ctx, hipGetLastError());

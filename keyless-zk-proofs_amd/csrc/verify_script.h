@@ -702,6 +702,149 @@ inline void coop_build_finalexp_program(const PairConsts& K, CoopProgram* P)
     coop_compile(B, out_node, COOP_FE_INPUTS, P);
 }
 
+// The split check (k16_prover_prove_*_verified, prover.hip): the per-proof check cut where the prover's data arrive.  A and B
+// are final while the GPU still works on the H MSM, C only after it, so
+//   EARLY  inputs A.x A.y | B.x.a B.x.b B.y.a B.y.b | vk_x as X ZZZ, Y ZZ, ZZ ZZZ      (COOP_EARLY_INPUTS slots)
+//          output: the multi-Miller value of (A, B) and (vk_x, -gamma), one squaring per digit -- NO final exponentiation
+//   LATE   inputs: those 12 Fq | C.x C.y                                                (COOP_LATE_INPUTS slots)
+//          output: final_exponentiation(early * miller(C, -delta)) -- the GT value of the per-proof program
+// Both use the per-proof program's constant table and slot numbering (zero, one, PairConsts, e(alpha, beta), the lines of
+// -gamma, the lines of -delta), so the key's table serves all three.  The raw early value is not canonical: vk_x's lines
+// carry the Fq factor sz (see coop_build_program); the final exponentiation removes it.
+constexpr uint32_t COOP_EARLY_INPUTS = 9;
+constexpr uint32_t COOP_LATE_INPUTS  = 14;
+namespace detail {
+struct SplitRecorder {
+    k16t::Builder    B;
+    k16t::PairConsts TK;
+    uint32_t         line_base = 0, n_lines = 0, in_base = 0;
+    k16t::Fq new_in(int32_t slot) { return k16t::Fq{B.add_node(k16t::N_IN, slot, -1)}; }
+    k16t::Fq inp(uint32_t k) { return new_in((int32_t)(in_base + k)); }
+    k16t::Ell line(uint32_t pair /* 1 or 2 */, uint32_t k)
+    {
+        const int32_t s = (int32_t)(line_base + ((pair - 1) * n_lines + k) * 6);
+        k16t::Ell     l;
+        l.c0 = k16t::Fq2{new_in(s), new_in(s + 1)};
+        l.c1 = k16t::Fq2{new_in(s + 2), new_in(s + 3)};
+        l.c2 = k16t::Fq2{new_in(s + 4), new_in(s + 5)};
+        return l;
+    }
+    // the constant slots exactly as coop_build_program numbers them
+    void begin(const PairConsts& K, CoopProgram* P)
+    {
+        k16t::cur() = &B;
+        B.zero_id   = new_in(0).id;
+        B.one_id    = new_in(1).id;
+        Fq pc[COOP_NPC];
+        coop_flatten_consts(K, pc);
+        uint32_t next = 2;
+        auto     cst = [&](const Fq& concrete) -> k16t::Fq {
+            const uint32_t s = next++;
+            if (concrete.is_zero()) return k16t::Fq::zero();
+            if (concrete == Fq::one()) return k16t::Fq::one();
+            return new_in((int32_t)s);
+        };
+        uint32_t n  = 0;
+        auto     g2 = [&]() {
+            k16t::Fq a = cst(pc[n]), b = cst(pc[n + 1]);
+            n += 2;
+            return k16t::Fq2{a, b};
+        };
+        TK.twist_b = g2();
+        TK.twqx    = g2();
+        TK.twqy    = g2();
+        for (int k = 0; k < 4; k++) TK.frob6_c1[k] = g2();
+        for (int k = 0; k < 4; k++) TK.frob6_c2[k] = g2();
+        for (int k = 0; k < 4; k++) TK.frob12_c1[k] = g2();
+        TK.two_inv      = cst(pc[n]);
+        n_lines         = coop_line_count();
+        P->target_const = next;
+        next += 12;
+        line_base = next;
+        next += 2 * n_lines * 6;
+        P->n_const = P->in_base = in_base = next;
+        P->n_lines                        = n_lines;
+    }
+    void finish(const k16t::Fp12& v, uint32_t n_inputs, CoopProgram* P)
+    {
+        const k16t::Fq2* ev = &v.c0.c0;
+        int32_t          out_node[12];
+        for (int i = 0; i < 6; i++) {
+            out_node[2 * i]     = ev[i].a.id;
+            out_node[2 * i + 1] = ev[i].b.id;
+        }
+        coop_compile(B, out_node, n_inputs, P);
+    }
+    ~SplitRecorder() { k16t::cur() = nullptr; }
+};
+} // namespace detail
+
+inline void coop_build_early_program(const PairConsts& K, CoopProgram* P)
+{
+    namespace t = k16t;
+    detail::SplitRecorder R;
+    R.begin(K, P);
+    t::Aff<t::Fq>  pa{R.inp(0), R.inp(1)};
+    t::Aff<t::Fq2> qb{t::Fq2{R.inp(2), R.inp(3)}, t::Fq2{R.inp(4), R.inp(5)}};
+    const t::Fq    vk_sx = R.inp(6), vk_sy = R.inp(7), vk_sz = R.inp(8);
+    t::Fp12        f = t::f12_one();
+    t::G2Hom       r{qb.x, qb.y, t::Fq2::one()};
+    t::Aff<t::Fq2> nq{qb.x, t::fneg(qb.y)};
+    t::Ell         l;
+    uint32_t       k = 0;
+    auto ells = [&]() { // the fixed pair first: its operands are ready early
+        const t::Ell l1 = R.line(1, k);
+        t::Fq2       c0 = t::fmul_fp(l1.c0, vk_sy), c1 = t::fmul_fp(l1.c1, vk_sx), c2 = t::fmul_fp(l1.c2, vk_sz);
+        t::f12_mul_by_034(&f, &c0, &c1, &c2);
+        t::f12_ell(&f, l, pa);
+        k++;
+    };
+    for (int i = (int)ATE_TOP; i >= 1; i--) {
+        if (i != (int)ATE_TOP) t::f12_sqr(&f, &f);
+        t::g2hom_double(&r, &l, &R.TK);
+        ells();
+        const unsigned d = (unsigned)(i - 1);
+        if ((ATE_NZ_LO >> d) & 1) {
+            t::g2hom_add(&r, ((ATE_NEG_LO >> d) & 1) ? &nq : &qb, &l);
+            ells();
+        }
+    }
+    t::Aff<t::Fq2> q1 = t::g2_mul_by_char(qb, R.TK);
+    t::Aff<t::Fq2> q2 = t::g2_mul_by_char(q1, R.TK);
+    q2.y              = t::fneg(q2.y);
+    t::g2hom_add(&r, &q1, &l);
+    ells();
+    t::g2hom_add(&r, &q2, &l);
+    ells();
+    if (k != R.n_lines) throw std::logic_error("coop early program: line count");
+    R.finish(f, COOP_EARLY_INPUTS, P);
+}
+
+inline void coop_build_late_program(const PairConsts& K, CoopProgram* P)
+{
+    namespace t = k16t;
+    detail::SplitRecorder R;
+    R.begin(K, P);
+    t::Fp12 early;
+    t::Fq2* fv = &early.c0.c0;
+    for (int i = 0; i < 6; i++) fv[i] = t::Fq2{R.inp(2 * i), R.inp(2 * i + 1)};
+    t::Aff<t::Fq> pc3{R.inp(12), R.inp(13)};
+    t::Fp12       g = t::f12_one();
+    uint32_t      k = 0;
+    for (int i = (int)ATE_TOP; i >= 1; i--) {
+        if (i != (int)ATE_TOP) t::f12_sqr(&g, &g);
+        t::f12_ell(&g, R.line(2, k++), pc3);
+        if ((ATE_NZ_LO >> (unsigned)(i - 1)) & 1) t::f12_ell(&g, R.line(2, k++), pc3);
+    }
+    t::f12_ell(&g, R.line(2, k++), pc3);
+    t::f12_ell(&g, R.line(2, k++), pc3);
+    if (k != R.n_lines) throw std::logic_error("coop late program: line count");
+    t::Fp12 f, e;
+    t::f12_mul(&f, &early, &g);
+    (void)t::final_exponentiation(&e, &f, &R.TK);
+    R.finish(e, COOP_LATE_INPUTS, P);
+}
+
 // ------------------------------------------------------------------------------------------------ host interpreter
 // Executes the program with the concrete field (tests; the device kernel is the same loop with lanes in parallel).
 inline void coop_run_host(const CoopProgram& P, std::vector<Fq>& slots /* constants + inputs filled in */)

@@ -44,6 +44,8 @@ SYMBOLS = [
     "k16_vk_create", "k16_vk_destroy", "k16_verify_batch", "k16_verify_coop_gt", "k16_pairing_vec",
     "k16_points_check", "k16_verify_batch_checked", "k16_zkey_check", "k16_zkey_check_file",
     "k16_verify_batch_folded", "k16_verify_fold_gt",
+    "k16_vk_create_from_zkey", "k16_vk_create_from_zkey_file", "k16_prover_set_vk", "k16_prover_prove_mem_verified",
+    "k16_prover_prove_compact_verified", "k16_prover_prove_file_verified", "k16_verify_split_gt", "k16_fullprover_set_verify",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
     "k16_msm_sharded_last_error", "k16_msm_sharded_set_bases", "k16_msm_sharded_set_bases_device", "k16_msm_sharded_run",
     "k16_msm_sharded_run_device", "k16_msm_sharded_set_piece_rows", "k16_msm_sharded_last_ms",
@@ -146,6 +148,14 @@ def load():
     L.k16_verify_batch_checked.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.k16_verify_batch_folded.argtypes = [vp, vp, vp, vp, u64, vp, vp, C.POINTER(C.c_uint8)]
     L.k16_verify_fold_gt.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.k16_vk_create_from_zkey.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    L.k16_vk_create_from_zkey_file.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
+    L.k16_prover_set_vk.argtypes = [vp, vp]
+    L.k16_prover_prove_mem_verified.argtypes = [vp, vp, u64, vp, vp, C.c_char_p, sz, C.POINTER(C.c_float), vp, C.POINTER(C.c_uint8)]
+    L.k16_prover_prove_compact_verified.argtypes = [vp, u64, vp, vp, C.c_char_p, sz, C.POINTER(C.c_float), vp, C.POINTER(C.c_uint8)]
+    L.k16_prover_prove_file_verified.argtypes = [vp, C.c_char_p, vp, vp, C.c_char_p, sz, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, C.POINTER(C.c_uint8)]
+    L.k16_fullprover_set_verify.argtypes = [vp, i32]
+    L.k16_verify_split_gt.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.k16_zkey_check.argtypes = [vp, vp, sz, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
     L.k16_zkey_check_file.argtypes = [vp, C.c_char_p, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
     L.k16_msm_sharded_create.argtypes = [C.POINTER(i32), i32, i32, u64, C.POINTER(vp)]
@@ -511,6 +521,38 @@ class Prover:
         self.last_device_ms = ms.value
         return buf.value.decode()
 
+    def set_vk(self, vk):
+        """k16_prover_set_vk: the VerifyingKey the *_verified calls check against (None detaches).  The prover does not own
+        it: keep it alive while it is attached."""
+        rc = self.ctx.L.k16_prover_set_vk(self.h, vk.h if vk is not None else None)
+        if rc < 0:
+            raise K16Error(rc, (self.ctx.L.k16_last_error(self.ctx.h) or b"").decode())
+
+    def _verified(self, call, r, s):
+        buf = C.create_string_buffer(4096)
+        ms = C.c_float()
+        R_ = np.frombuffer(bytes(r), dtype=np.uint8).copy() if r is not None else None
+        S_ = np.frombuffer(bytes(s), dtype=np.uint8).copy() if s is not None else None
+        proof = np.zeros(256, dtype=np.uint8)
+        ok = C.c_uint8(0)
+        rc = call(_p(R_), _p(S_), buf, 4096, C.byref(ms), _p(proof), C.byref(ok))
+        if rc < 0:
+            raise K16Error(rc, (self.ctx.L.k16_last_error(self.ctx.h) or b"").decode())
+        self.last_device_ms = ms.value
+        return buf.value.decode(), proof.tobytes(), int(ok.value)
+
+    def prove_mem_verified(self, wtns, r=None, s=None):
+        """k16_prover_prove_mem_verified: (json, proof_bytes, ok) -- prove_mem's JSON, the proof as 256 bytes A | B | C in
+        VerifyingKey.verify_batch's format, and that call's flag for it with the witness's public inputs."""
+        wtns = np.ascontiguousarray(wtns, dtype=np.uint8)
+        L, h, n_vars = self.ctx.L, self.h, wtns.size // 32
+        return self._verified(lambda *a: L.k16_prover_prove_mem_verified(h, _p(wtns), n_vars, *a), r, s)
+
+    def prove_compact_verified(self, n_wide, r=None, s=None):
+        """k16_prover_prove_compact_verified: as prove_mem_verified, for the witness compact_buffers() holds."""
+        L, h = self.ctx.L, self.h
+        return self._verified(lambda *a: L.k16_prover_prove_compact_verified(h, int(n_wide), *a), r, s)
+
     def warmup_status(self):
         return int(self.ctx.L.k16_prover_warmup_status(self.h))
 
@@ -526,6 +568,21 @@ class Prover:
             self.h = None
 
 
+def _zkey_n_public(head):
+    """nPublic from the start of an iden3 zkey (section 2 of a Groth16 key: n8q, q, n8r, r, nVars, nPublic, ...)."""
+    nsec = int.from_bytes(head[8:12], "little")
+    pos = 12
+    for _ in range(nsec):
+        if pos + 12 > len(head):
+            break
+        typ, size = int.from_bytes(head[pos:pos + 4], "little"), int.from_bytes(head[pos + 4:pos + 12], "little")
+        if typ == 2:
+            o = pos + 12 + 4 + 32 + 4 + 32 + 4
+            return int.from_bytes(head[o:o + 4], "little")
+        pos += 12 + size
+    raise ValueError("zkey: section 2 not within the first %d bytes" % len(head))
+
+
 class VerifyingKey:
     """Groth16 verifying key resident on the GPU (k16_vk_create) + batched verification (k16_verify_batch): the mirror of
     the service's prepared_vk / verify_proof pair (prover-service/src/request_handler/types.rs:141-196,
@@ -539,6 +596,41 @@ class VerifyingKey:
         ctx._chk(ctx.L.k16_vk_create(ctx.h, _p(b(vk["alpha1"])), _p(b(vk["beta2"])), _p(b(vk["gamma2"])), _p(b(vk["delta2"])),
                                      _p(ic), self.n_ic, C.byref(h)))
         self.h = h
+
+    @classmethod
+    def from_zkey(cls, ctx, path_or_bytes):
+        """The key a proving key carries (k16_vk_create_from_zkey[_file]): alpha1, beta2, gamma2, delta2 of section 2 and IC
+        of section 3.  path_or_bytes: a file name, or the zkey's bytes."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        h = C.c_void_p()
+        if isinstance(path_or_bytes, str):
+            rc = ctx.L.k16_vk_create_from_zkey_file(ctx.h, path_or_bytes.encode(), C.byref(h))
+            with open(path_or_bytes, "rb") as f:
+                head = f.read(4096)
+        else:
+            z = np.frombuffer(bytes(path_or_bytes), dtype=np.uint8).copy()
+            rc = ctx.L.k16_vk_create_from_zkey(ctx.h, _p(z), z.size, C.byref(h))
+            head = bytes(path_or_bytes[:4096])
+        if rc:
+            raise K16Error(rc, (ctx.L.k16_last_error(ctx.h) or b"").decode())
+        self.h = h
+        self.n_ic = _zkey_n_public(head) + 1
+        return self
+
+    def split_gt(self, proofs, inputs):
+        """k16_verify_split_gt (n <= 64): the split check's two values per proof -- (early, gt), each (n, 384) uint8: the
+        multi-Miller value of (A,B), (vk_x,-gamma) before any final exponentiation, and the GT value coop_gt also gives.
+        Raises K16Error(ARG) for a proof that fails the point checks, has a zero point, or whose vk_x is infinity."""
+        n = len(proofs)
+        pr = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8).copy()
+        inp = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for row in inputs for x in row), dtype=np.uint8).copy()
+        early = np.zeros((n, 384), dtype=np.uint8)
+        gt = np.zeros((n, 384), dtype=np.uint8)
+        rc = self.ctx.L.k16_verify_split_gt(self.ctx.h, self.h, _p(pr), _p(inp) if inp.size else None, n, _p(early), _p(gt))
+        if rc < 0:
+            raise K16Error(rc, (self.ctx.L.k16_last_error(self.ctx.h) or b"").decode())
+        return early, gt
 
     def verify_batch(self, proofs, inputs):
         """proofs: list of 256-byte A | B | C; inputs: per proof a list of n_ic - 1 ints.  Returns a list of bools."""
