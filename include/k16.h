@@ -519,6 +519,49 @@ int  k16_zkey_check(k16_ctx* ctx, const void* zkey, size_t size, uint32_t* bad_s
 int  k16_zkey_check_file(k16_ctx* ctx, const char* zkey_path, uint32_t* bad_section, uint64_t* bad_index,
                          uint8_t* bad_status, uint64_t* n_bad);
 
+/* ---- R1CS witness check: WHICH constraints does a witness break? ----
+ * A verified prove (above) can only say that a proof was rejected; a zkey cannot say more, its section 4 holds A and B alone.
+ * With the circuit's .r1cs file (iden3 container: header section 1, constraints section 2, coefficients in standard form;
+ * csrc/r1cs_file.h) the check is (A.w) o (B.w) - C.w = 0, evaluated on the GPU in the prover's own field code: three sparse
+ * matrix-vector products in one launch and one pointwise pass (csrc/r1cs_check.hip).
+ * k16_r1cs_create* parse and upload a circuit once: K16_ERR_FORMAT for a malformed file (truncation, a count that runs past its
+ * section, a wire >= nWires, a coefficient >= r, bytes left over, a header with nWires = 0 or nPubOut + nPubIn >= nWires),
+ * K16_ERR_CURVE when the field is not BN254's Fr, K16_ERR_ARG for
+ * 2^32 / 3 constraints or more, or 2^32 or more (padded) terms.  A wire listed twice in a combination is legal: its coefficients add.
+ * The check calls: *n_failed = number of broken constraints (0: the witness satisfies the circuit); h_failed (may be NULL) receives
+ * the lowest min(*n_failed, cap) constraint numbers, ascending -- the same list for every run.
+ *   k16_r1cs_check_mem             h_wtns: n_wires x 32 B standard form (the payload of wtns section 2); K16_ERR_ARG unless
+ *                                  n_wires is the circuit's
+ *   k16_r1cs_check_file            a .wtns file, under the container and curve checks of k16_prover_prove_file; K16_ERR_FORMAT
+ *                                  when it does not hold exactly the circuit's number of values
+ *   k16_r1cs_check_prover_witness  the witness of the prover's LAST prove call, read where it lies on the device -- no upload.
+ *                                  K16_ERR_ARG unless that call succeeded (k16_prover_prove_mem / _file / _compact and their
+ *                                  _verified forms alike: an accepted and a rejected proof both leave the whole witness; a
+ *                                  failed or aborted call does not, nor does the warm-up of k16_prover_create), unless the
+ *                                  R1CS object lives on the prover's context and unless its nWires is the key's nVars.
+ * A witness is REFUSED with K16_ERR_FORMAT, whatever its constraints say, when a wire value is >= r (checked on the device) or
+ * when wire 0 is not 1: every constraint can hold for such an assignment, yet no proof of it verifies.
+ * THREADING: one check at a time per object, on the context's stream, under the context's one-caller rule.  Every error leaves
+ * nothing in flight. */
+typedef struct k16_r1cs k16_r1cs;
+int  k16_r1cs_create(k16_ctx* ctx, const char* path, k16_r1cs** out);
+int  k16_r1cs_create_mem(k16_ctx* ctx, const void* r1cs, size_t size, k16_r1cs** out);
+void k16_r1cs_destroy(k16_r1cs* r);
+int  k16_r1cs_info(const k16_r1cs* r, uint32_t* n_wires, uint32_t* n_public, uint32_t* n_constraints, uint64_t* n_terms);
+int  k16_r1cs_check_mem(k16_ctx* ctx, k16_r1cs* r, const void* h_wtns, uint64_t n_wires, uint64_t* n_failed, uint32_t* h_failed,
+                        uint32_t cap);
+int  k16_r1cs_check_file(k16_ctx* ctx, k16_r1cs* r, const char* wtns_path, uint64_t* n_failed, uint32_t* h_failed, uint32_t cap);
+int  k16_r1cs_check_prover_witness(k16_prover* p, k16_r1cs* r, uint64_t* n_failed, uint32_t* h_failed, uint32_t cap);
+/* A.w | B.w | C.w of one constraint as the LAST completed check computed them, 3 x 32 B standard form, canonical.  K16_ERR_ARG
+ * when no check has completed on the object (a refused witness completes none) or the constraint number is out of range. */
+int  k16_r1cs_last_values(k16_r1cs* r, uint32_t constraint, void* h_out96);
+/* Do this circuit and this proving key belong together?  Host only.  Section 4 of a snarkjs Groth16 zkey is derived from the
+ * circuit: per term of A and B a record { matrix, constraint, wire, coefficient * 2^512 mod r } plus one row per public wire
+ * (and the constant) behind the last constraint.  *mismatch = 0: the zkey's section 4 and header (nVars, nPublic, a power-of-two
+ * domain that holds the rows) are this circuit's; else the kind of the first difference -- 1 header, 2 matrix A, 3 matrix B,
+ * 4 public rows -- with its constraint and wire in k16_last_error.  K16_ERR_FORMAT / K16_ERR_CURVE for an unreadable zkey. */
+int  k16_r1cs_match_zkey(k16_ctx* ctx, const k16_r1cs* r, const void* zkey, size_t size, uint32_t* mismatch);
+
 #ifdef __cplusplus
 }
 #endif

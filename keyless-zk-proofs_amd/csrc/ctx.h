@@ -295,6 +295,18 @@ struct k16_stat_scope {
     }
 };
 
+// host-side helpers implemented in prover.hip, for r1cs_check.hip
+// maps a file read-only and calls fn(base, size); unmapped when fn returns, whose status is returned.  K16_ERR_IO /
+// K16_ERR_FORMAT (an empty file) with "<what>: cannot open/map <path>" as the context's error text.
+int k16_file_apply(k16_ctx* ctx, const char* path, const char* what, const std::function<int(const uint8_t*, size_t)>& fn);
+// maps a .wtns file, applies the container / curve checks of k16_prover_prove_file and calls fn(values, n_values) with the
+// payload of section 2 (n_values x 32 B standard form); the file is unmapped when fn returns.  fn's status is returned.
+int k16_wtns_file_apply(k16_ctx* ctx, const char* wtns_path, const std::function<int(const uint8_t*, uint64_t)>& fn);
+// The witness of p's last prove call where it lies on the device: 32-byte standard-form values and the n16 words of k_spmv.
+// K16_ERR_ARG (with the context's error text) unless that call succeeded -- plain or compact upload alike; a failed or
+// aborted prove leaves the buffers incomplete.
+int k16_prover_witness_view(k16_prover* p, k16_ctx** ctx, const k16::Fr** d_wtns, const uint16_t** d_n16, uint32_t* n_vars);
+
 // host-side helpers implemented in ntt.hip
 int k16_ntt_get_table(k16_ctx* ctx, uint64_t max_domain, k16_ntt_table** out);
 // packed9: bit 0 = data is in the packed R' domain, bit 1 = input already bit-reversed, bit 2 = skip the inverse tail

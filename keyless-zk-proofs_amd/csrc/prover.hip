@@ -34,6 +34,7 @@
 #include "points_check.h"
 #include "bn254_fq9.h"
 #include "spmv_plan.h"
+#include "spmv_dev.h"
 #include "verify_split.h"
 
 using namespace k16;
@@ -103,38 +104,7 @@ struct MappedFile {
 };
 
 // ---------------------------------------------------------------- device kernels (F12, F13)
-__device__ __forceinline__ Fr ld_fr(const Fr* p)
-{
-    Fr           r;
-    const uint4* s = reinterpret_cast<const uint4*>(p);
-    uint4        a = s[0], b = s[1];
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-__device__ __forceinline__ void st_fr(Fr* p, const Fr& r)
-{
-    uint4* d = reinterpret_cast<uint4*>(p);
-    d[0]     = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    d[1]     = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-
-// The polynomial chain works on the radix-2^29 representation of Fr (bn254_fq9.h): a, b, c live in HBM as
-// packed R' values (x * 2^261 mod r, < 2r, 32 bytes), the coefficients are stored pre-multiplied by 2^522
-// (the reference's zkey stores them pre-multiplied by R^2 = 2^512 for the same reason), and only the
-// final H scalars are brought back to the canonical standard form the MSM consumes.  Field values are exact
-// mod r throughout, so the H scalars are bit-identical to the reference's (tests compare them).
-__device__ __forceinline__ Fr9 ld_r9(const Fr* p)
-{
-    Fr w = ld_fr(p);
-    return fr9_load(w.v);
-}
-__device__ __forceinline__ void st_r9(Fr* p, const Fr9& v)
-{
-    Fr w;
-    fr9_store(w.v, v);
-    st_fr(p, w);
-}
+// (ld_fr / st_fr, ld_r9 / st_r9 and the row walk itself live in spmv_dev.h, shared with r1cs_check.hip)
 // groth16.cpp:137-156 : ab[c] += wtns[s] (x) coef.  The zkey's coefficient list is regrouped once at load time into rows
 // (matrix m, constraint c), so each output element has one owner and no 256-bit atomics / spinlocks are needed.  Field
 // addition is exact, so the summation order is free.  Layout (k16_prover_create): rows of up to SPMV_LONG entries are
@@ -158,43 +128,8 @@ __global__ void __launch_bounds__(256) k_spmv(const SpmvSlice* __restrict__ slic
                                               const uint16_t* __restrict__ n16)
 {
     __builtin_amdgcn_s_setprio(K16_CHAIN_PRIO); // the polynomial chain gates the H MSM: its waves win VALU arbitration beside the witness MSMs
-    const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    Fr9            acc = fq9_zero();
-    // n16 (round 4): one 16-bit word per wire -- the value when it is below 256, bit 15 when it is not.  98 % of a circuit's
-    // wires are bits and bytes: the walk's dependent gather then hits a 2.7 MB array (L2) instead of the 43 MB witness, and
-    // the product is a single-limb multiplication; only the wide wires load their 32 bytes.  Same integers, same limbs.
-    auto term = [&](uint32_t e) -> Fr9 {
-        const uint32_t wi = wire[e];
-        if (n16) {
-            const uint32_t c = n16[wi];
-            if (!(c & 0x8000u)) return fmul9_small_t<Fr9C>(ld_r9(&coef9[e]), c);
-        }
-        return frmul9(ld_r9(&wtns[wi]), ld_r9(&coef9[e]));
-    };
-    if (w < n_slices) {
-        const SpmvSlice sl = slices[w];
-        for (uint32_t k = 0; k < sl.len; k++) {
-            const uint32_t e = sl.off + (k << 6) + lane; // padding entries: wire 0, coefficient 0
-            acc = fradd9(acc, term(e));
-        }
-        const uint32_t row = row_of[(w << 6) + lane];
-        if (row != 0xffffffffu) spmv_store(a, b, row, N, logN, acc);
-        return;
-    }
-    if (w - n_slices >= n_long) return;
-    const SpmvLong L = longs[w - n_slices];
-    for (uint32_t k = lane; k < L.len; k += 64) {
-        const uint32_t e = L.off + k;
-        acc = fradd9(acc, term(e));
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        Fr9 o;
-#pragma unroll
-        for (int i = 0; i < 9; i++) o.l[i] = (uint32_t)__shfl_xor((int)acc.l[i], d, 64);
-        acc = fradd9(acc, o);
-    }
-    if (lane == 0) spmv_store(a, b, L.row, N, logN, acc);
+    spmv_walk(slices, n_slices, row_of, longs, n_long, wire, coef9, wtns, n16,
+              [&](uint32_t row, const Fr9& acc) { spmv_store(a, b, row, N, logN, acc); });
 }
 // groth16.cpp:160-167
 __global__ void __launch_bounds__(256) k_mul(Fr* __restrict__ c, const Fr* __restrict__ a, const Fr* __restrict__ b,
@@ -447,6 +382,9 @@ struct k16_prover {
     bool  b_sort    = false;
     bool  b_derive  = false; // B1 / B2 accumulate bucket lists of their own, derived from A's partition without their (0,0) rows
     const k16_vk* vk = nullptr; // k16_prover_set_vk: what the _verified prove calls check their proofs against (not owned)
+    // d_wtns / d_n16 hold the complete witness of the last prove call: set by a prove that succeeded (plain or compact
+    // upload), cleared when one starts -- a failed or aborted prove leaves them half written (k16_prover_witness_view)
+    bool wtns_complete = false;
 };
 
 // Host side of the compact upload: the context's host threads (k16_ctx_pool) each scan a contiguous range of the witness.
@@ -915,6 +853,7 @@ static int prover_finish_create(k16_prover* p, k16_prover** out)
             fprintf(stderr, "k16_prover_create: warm-up proof failed (%d): %s\n", wrc, ctx->err.c_str());
             p->warmup_rc = wrc;
         }
+        p->wtns_complete = false; // (the discarded warm-up is no prove call of the caller's)
     }
     *out = p;
     return K16_OK;
@@ -957,6 +896,7 @@ extern "C" int k16_prover_create_shared(k16_ctx* ctx, const k16_prover* other, k
     p->cls    = nullptr;
     p->last_h.clear();
     p->warmup_rc = 0;
+    p->wtns_complete = false;
     const size_t   nv = p->n_vars;
     const uint32_t N  = p->domain_size;
     K16_HIP_P(ctx, hipSetDevice(ctx->device), p);
@@ -1141,6 +1081,7 @@ static int prove_guarded(k16_prover* p, const void* h_wtns, uint64_t n_vars, int
 {
     return k16_guard((p ? p->ctx : nullptr), [&]() -> int {
     if (!p || (!h_wtns && prepacked < 0) || !out_json) return K16_ERR_ARG;
+    p->wtns_complete = false;
     int rc;
     try {
         rc = prove_mem_inner(p, h_wtns, n_vars, prepacked, r_in, s_in, out_json, cap, device_ms, vr);
@@ -1173,6 +1114,7 @@ static int prove_guarded(k16_prover* p, const void* h_wtns, uint64_t n_vars, int
         } catch (...) {
         }
     }
+    p->wtns_complete = rc >= 0;
     return rc;
     });
 }
@@ -1705,6 +1647,59 @@ extern "C" int k16_vk_create_from_zkey_file(k16_ctx* ctx, const char* zkey_path,
     });
 }
 
+// a file mapped read-only for the duration of fn (ctx.h)
+int k16_file_apply(k16_ctx* ctx, const char* path, const char* what, const std::function<int(const uint8_t*, size_t)>& fn)
+{
+    MappedFile mf;
+    const int  rc = mf.open_ro(path);
+    if (rc) {
+        ctx->err = std::string(what) + ": cannot open/map " + path;
+        return rc;
+    }
+    return fn(mf.base, mf.size);
+}
+// A .wtns file mapped, its container and header checked, its values handed to fn (ctx.h): what k16_prover_prove_file and
+// k16_r1cs_check_file both do before they look at a value.
+int k16_wtns_file_apply(k16_ctx* ctx, const char* wtns_path, const std::function<int(const uint8_t*, uint64_t)>& fn)
+{
+    return k16_file_apply(ctx, wtns_path, "wtns", [&](const uint8_t* base, size_t size) -> int {
+    BinView bv;
+    int     rc = parse_binfile(base, size, "wtns", 2, &bv); // fullprover.cpp:212
+    if (rc || !bv.sec[1].p || !bv.sec[2].p || bv.sec[1].size < 4 + 32 + 4) {
+        ctx->err = "wtns: malformed container";
+        return K16_ERR_FORMAT;
+    }
+    // wtns_utils.hpp:32-40, fullprover.cpp:216-221
+    uint32_t n8 = 0;
+    memcpy(&n8, bv.sec[1].p, 4);
+    if (n8 != 32 || memcmp(bv.sec[1].p + 4, BN254_R_LE, 32) != 0) {
+        ctx->err = "witness uses a different curve than bn128";
+        return K16_ERR_CURVE;
+    }
+    // (the header's nVars is not trusted -- the reference does not even compare it with the key's, SURVEY 8(b): the
+    // section's own length says how many values there are, and the consumer checks that against the circuit)
+    return fn(bv.sec[2].p, bv.sec[2].size / 32);
+    });
+}
+
+// the witness of the prover's last prove call, in place on the device (ctx.h; k16_r1cs_check_prover_witness)
+int k16_prover_witness_view(k16_prover* p, k16_ctx** ctx, const Fr** d_wtns, const uint16_t** d_n16, uint32_t* n_vars)
+{
+    if (!p) return K16_ERR_ARG;
+    *ctx    = p->ctx;
+    *d_wtns = p->d_wtns;
+    *d_n16  = p->d_n16;
+    *n_vars = p->n_vars;
+    if (!p->wtns_complete) {
+        try {
+            p->ctx->err = "the prover holds no complete witness: its last prove call failed, or there was none";
+        } catch (...) {
+        }
+        return K16_ERR_ARG;
+    }
+    return K16_OK;
+}
+
 extern "C" int k16_prover_prove_file(k16_prover* p, const char* wtns_path, const uint8_t* r_std, const uint8_t* s_std,
                                      char* out_json, size_t cap, float* device_ms)
 {
@@ -1737,34 +1732,13 @@ static int prove_file_inner(k16_prover* p, const char* wtns_path, const uint8_t*
     return k16_guard((p ? p->ctx : nullptr), [&]() -> int {
     if (prove_wall_ms) *prove_wall_ms = 0.f;
     if (!p || !wtns_path) return K16_ERR_ARG;
-    k16_ctx*   ctx = p->ctx;
-    MappedFile mf;
-    int        rc = mf.open_ro(wtns_path);
-    if (rc) {
-        ctx->err = std::string("wtns: cannot open/map ") + wtns_path;
-        return rc;
-    }
-    BinView bv;
-    rc = parse_binfile(mf.base, mf.size, "wtns", 2, &bv); // fullprover.cpp:212
-    if (rc || !bv.sec[1].p || !bv.sec[2].p || bv.sec[1].size < 4 + 32 + 4) {
-        ctx->err = "wtns: malformed container";
-        return K16_ERR_FORMAT;
-    }
-    // wtns_utils.hpp:32-40, fullprover.cpp:216-221
-    uint32_t n8 = 0;
-    memcpy(&n8, bv.sec[1].p, 4);
-    if (n8 != 32 || memcmp(bv.sec[1].p + 4, BN254_R_LE, 32) != 0) {
-        ctx->err = "witness uses a different curve than bn128";
-        return K16_ERR_CURVE;
-    }
-    // (the header's nVars is not trusted -- the reference does not even compare it with the key's, SURVEY 8(b): the
-    // section's own length says how many values there are, and prove_mem checks that against the circuit)
-    uint64_t have = bv.sec[2].size / 32;
+    return k16_wtns_file_apply(p->ctx, wtns_path, [&](const uint8_t* values, uint64_t have) -> int {
     const auto t0 = std::chrono::steady_clock::now();
-    rc            = verified ? k16_prover_prove_mem_verified(p, bv.sec[2].p, have, r_std, s_std, out_json, cap, device_ms, out_proof, out_ok)
-                             : k16_prover_prove_mem(p, bv.sec[2].p, have, r_std, s_std, out_json, cap, device_ms);
+    const int  rc = verified ? k16_prover_prove_mem_verified(p, values, have, r_std, s_std, out_json, cap, device_ms, out_proof, out_ok)
+                           : k16_prover_prove_mem(p, values, have, r_std, s_std, out_json, cap, device_ms);
     if (prove_wall_ms) *prove_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
+    });
     });
 }
 

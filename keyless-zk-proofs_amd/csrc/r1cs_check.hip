@@ -1,0 +1,370 @@
+// r1cs_check.hip -- the R1CS witness check on the GPU (include/k16.h, k16_r1cs_*): which constraints of a circuit does a
+// witness break?  (A.w) o (B.w) - C.w = 0 is three sparse matrix-vector products over Fr and one pointwise pass:
+//   k_r1cs_rows    k_spmv's walk (spmv_dev.h) over the 3 M rows A | B | C of the circuit's .r1cs file (r1cs_file.h: length-sorted
+//                  slices + a wave per long row), the sum of row id = matrix * M + constraint stored at index id as a packed
+//                  R' value -- no bit reversal, no transform follows
+//   k_r1cs_judge   one lane per constraint: a * b - c brought to the canonical standard form and compared with zero (the sums
+//                  are lazy representatives below 2r: only the canonical form tells r from 0); a wave's verdicts leave as one
+//                  64-bit ballot word, written by one lane
+// Two kernels because the judge needs all three sums of a constraint and the rows are placed by LENGTH: A_c, B_c and C_c sit in
+// different slices, waves and workgroups.  The host reads the mask: an exact count and the failing constraints in ascending
+// order, the same for every run (an atomically appended list would come in a different order each time).
+// A witness with a wire >= r, or with wire 0 != 1, is refused (K16_ERR_FORMAT) by k_r1cs_wtns, the pass that also makes the
+// n16 words of an uploaded witness: every constraint can hold for an assignment with wire 0 = 2, yet no proof of it verifies.
+#include <stdio.h>
+#include <string.h>
+#include <memory>
+#include <string>
+#include <vector>
+#include "ctx.h"
+#include "r1cs_file.h"
+#include "spmv_dev.h"
+
+using namespace k16;
+
+static_assert(R1CS_ERR_ARG == K16_ERR_ARG && R1CS_ERR_FORMAT == K16_ERR_FORMAT && R1CS_ERR_CURVE == K16_ERR_CURVE && R1CS_OK == K16_OK,
+              "r1cs_file.h returns the library's status codes");
+
+namespace {
+
+enum : unsigned long long { WTNS_NOT_BELOW_R = 1, WTNS_WIRE0_NOT_ONE = 2 };
+
+// every wire: below r? wire 0: one?  n16 (may be null: the prover made it already) as k_wtns_n16 of prover.hip makes it
+__global__ void __launch_bounds__(256) k_r1cs_wtns(const uint4* __restrict__ wtns, uint32_t n, uint16_t* __restrict__ n16,
+                                                   unsigned long long* __restrict__ flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4    lo = wtns[2 * (size_t)i], hi = wtns[2 * (size_t)i + 1];
+    const bool     wide = ((lo.x >> 8) | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) != 0;
+    if (n16) n16[i] = wide ? (uint16_t)0x8000u : (uint16_t)lo.x;
+    unsigned long long bad = 0;
+    if (hi.w >= FrParams::P[7]) { // (only then can the value reach r)
+        const uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        bool           geq  = true;
+        for (int k = 7; k >= 0; k--) {
+            if (v[k] != FrParams::P[k]) {
+                geq = v[k] > FrParams::P[k];
+                break;
+            }
+        }
+        if (geq) bad |= WTNS_NOT_BELOW_R;
+    }
+    if (i == 0 && (wide || lo.x != 1u)) bad |= WTNS_WIRE0_NOT_ONE;
+    if (bad) atomicOr(flags, bad);
+}
+
+__global__ void __launch_bounds__(256) k_r1cs_rows(const SpmvSlice* __restrict__ slices, uint32_t n_slices,
+                                                   const uint32_t* __restrict__ row_of, const SpmvLong* __restrict__ longs,
+                                                   uint32_t n_long, const uint32_t* __restrict__ wire,
+                                                   const Fr* __restrict__ coef9, const Fr* __restrict__ wtns,
+                                                   const uint16_t* __restrict__ n16, Fr* __restrict__ rows)
+{
+    spmv_walk(slices, n_slices, row_of, longs, n_long, wire, coef9, wtns, n16,
+              [&](uint32_t row, const Fr9& acc) { st_r9(&rows[row], acc); });
+}
+
+// rows: A.w | B.w | C.w, M packed R' values each.  mask: n_words = ceil(M / 64) words, bit c % 64 of word c / 64 = constraint
+// c is broken; lanes beyond M vote 0.  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_judge(const Fr* __restrict__ rows, uint32_t M, uint32_t n_words,
+                                                    unsigned long long* __restrict__ mask)
+{
+    const uint32_t i    = blockIdx.x * blockDim.x + threadIdx.x;
+    bool           fail = false;
+    if (i < M) {
+        const Fr d = fr9_to_standard(frsub9(frmul9(ld_r9(&rows[i]), ld_r9(&rows[(size_t)M + i])), ld_r9(&rows[2 * (size_t)M + i])));
+        fail       = (d.v[0] | d.v[1] | d.v[2] | d.v[3] | d.v[4] | d.v[5] | d.v[6] | d.v[7]) != 0;
+    }
+    const unsigned long long votes = __ballot(fail);
+    if ((threadIdx.x & 63u) == 0 && (i >> 6) < n_words) mask[i >> 6] = votes;
+}
+
+} // namespace
+
+struct k16_r1cs {
+    k16_ctx* ctx = nullptr;
+    R1csFile file; // the host copy: k16_r1cs_match_zkey compares it with a key
+    uint32_t n_wires = 0, n_public = 0, M = 0, n_words = 0;
+    // the circuit on the device (see k_r1cs_rows)
+    SpmvSlice* d_slices = nullptr;
+    SpmvLong*  d_longs  = nullptr;
+    uint32_t * d_rowof = nullptr, *d_wire = nullptr;
+    Fr*        d_coef  = nullptr; // coefficient * 2^522 mod r, as the prover stores its own
+    uint32_t   n_slices = 0, n_long = 0;
+    // per check
+    Fr*                 d_wtns = nullptr; // an uploaded witness (k16_r1cs_check_mem / _file)
+    uint16_t*           d_n16  = nullptr;
+    Fr*                 d_rows = nullptr; // [3 M]
+    unsigned long long* d_mask = nullptr; // [n_words] verdicts | [1] witness flags
+    unsigned long long* h_mask = nullptr; // pinned copy
+    bool                have_values = false; // d_rows holds the sums of a completed check (k16_r1cs_last_values)
+};
+
+static void r1cs_free(k16_r1cs* r)
+{
+    if (!r) return;
+    if (r->ctx) (void)hipSetDevice(r->ctx->device);
+    void* bufs[] = {r->d_slices, r->d_longs, r->d_rowof, r->d_wire, r->d_coef, r->d_wtns, r->d_n16, r->d_rows, r->d_mask};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (r->h_mask) (void)hipHostFree(r->h_mask);
+    delete r;
+}
+
+#define K16_HIP_R(ctx, call, r)                                             \
+    do {                                                                    \
+        hipError_t e_ = (call);                                             \
+        if (e_ != hipSuccess) {                                             \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+            (void)hipStreamSynchronize((ctx)->stream); /* uploads from local vectors may be queued */ \
+            r1cs_free(r);                                                   \
+            return K16_ERR_HIP;                                             \
+        }                                                                   \
+    } while (0)
+
+extern "C" int k16_r1cs_create_mem(k16_ctx* ctx, const void* r1cs, size_t size, k16_r1cs** out)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !r1cs || !out) return K16_ERR_ARG;
+    *out = nullptr;
+    std::unique_ptr<k16_r1cs> holder(new k16_r1cs()); // (plain members only until the device buffers exist)
+    k16_r1cs*                 r = holder.get();
+    const char*               why = "";
+    int                       rc  = r1cs_parse((const uint8_t*)r1cs, size, &r->file, &why);
+    if (rc) {
+        ctx->err = why;
+        return rc;
+    }
+    R1csPlan plan;
+    if ((rc = r1cs_plan_build(r->file, &plan))) {
+        ctx->err = "r1cs: too many terms for 32-bit entry offsets";
+        return rc;
+    }
+    r->n_wires  = r->file.n_wires;
+    r->n_public = r->file.n_public();
+    r->M        = r->file.n_constraints;
+    r->n_words  = (uint32_t)(((uint64_t)r->M + 63) / 64);
+    r->n_slices = plan.plan.n_slices;
+    r->n_long   = plan.plan.n_long;
+    const uint64_t        n_entries = std::max<uint64_t>(plan.plan.n_entries, 1);
+    std::vector<uint32_t> wire(n_entries, 0);
+    std::vector<R1csFr>   vals(n_entries, R1csFr{{0, 0, 0, 0}}); // padding: coefficient 0 (times wire 0)
+    const R1csScale       to_r9(522);
+    for (uint64_t t = 0; t < r->file.n_terms(); t++) {
+        wire[plan.pos[t]] = r->file.wire[t];
+        vals[plan.pos[t]] = to_r9(r->file.coef[t]);
+    }
+    r->ctx = ctx;
+    holder.release(); // from here on r1cs_free owns it
+    K16_HIP_R(ctx, hipSetDevice(ctx->device), r);
+    const SpmvPlan& pl = plan.plan;
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_slices, pl.slices.size() * sizeof(SpmvSlice)), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_longs, pl.longs.size() * sizeof(SpmvLong)), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_rowof, pl.row_of.size() * 4), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_wire, wire.size() * 4), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_coef, vals.size() * 32), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_wtns, (size_t)r->n_wires * 32), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_n16, (size_t)r->n_wires * 2 + 64), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_rows, std::max<size_t>(3 * (size_t)r->M, 1) * 32), r);
+    K16_HIP_R(ctx, hipMalloc((void**)&r->d_mask, ((size_t)r->n_words + 1) * 8), r);
+    K16_HIP_R(ctx, hipHostMalloc((void**)&r->h_mask, ((size_t)r->n_words + 1) * 8, hipHostMallocDefault), r);
+    hipStream_t st = ctx->stream;
+    K16_HIP_R(ctx, hipMemcpyAsync(r->d_slices, pl.slices.data(), pl.slices.size() * sizeof(SpmvSlice), hipMemcpyHostToDevice, st), r);
+    K16_HIP_R(ctx, hipMemcpyAsync(r->d_longs, pl.longs.data(), pl.longs.size() * sizeof(SpmvLong), hipMemcpyHostToDevice, st), r);
+    K16_HIP_R(ctx, hipMemcpyAsync(r->d_rowof, pl.row_of.data(), pl.row_of.size() * 4, hipMemcpyHostToDevice, st), r);
+    K16_HIP_R(ctx, hipMemcpyAsync(r->d_wire, wire.data(), wire.size() * 4, hipMemcpyHostToDevice, st), r);
+    K16_HIP_R(ctx, hipMemcpyAsync(r->d_coef, vals.data(), vals.size() * 32, hipMemcpyHostToDevice, st), r);
+    K16_HIP_R(ctx, hipStreamSynchronize(st), r);
+    *out = r;
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_r1cs_create(k16_ctx* ctx, const char* path, k16_r1cs** out)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !path || !out) return K16_ERR_ARG;
+    *out = nullptr;
+    return k16_file_apply(ctx, path, "r1cs", [&](const uint8_t* base, size_t size) { return k16_r1cs_create_mem(ctx, base, size, out); });
+    });
+}
+
+extern "C" void k16_r1cs_destroy(k16_r1cs* r)
+{
+    k16_guard_void([&]() {
+        if (r && r->ctx && r->ctx->stream) (void)hipStreamSynchronize(r->ctx->stream);
+        r1cs_free(r);
+    });
+}
+
+extern "C" int k16_r1cs_info(const k16_r1cs* r, uint32_t* n_wires, uint32_t* n_public, uint32_t* n_constraints, uint64_t* n_terms)
+{
+    if (!r) return K16_ERR_ARG;
+    if (n_wires) *n_wires = r->n_wires;
+    if (n_public) *n_public = r->n_public;
+    if (n_constraints) *n_constraints = r->M;
+    if (n_terms) *n_terms = r->file.n_terms();
+    return K16_OK;
+}
+
+// The check proper, on the context's stream: d_wtns holds n_wires values; d_n16 their 16-bit words, or null when this call
+// is to make them (into r->d_n16).  Whatever fails, the stream is drained before the call returns.
+static int r1cs_enqueue(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint16_t* d_n16)
+{
+    hipStream_t st = ctx->stream;
+    K16_HIP(ctx, hipMemsetAsync(r->d_mask + r->n_words, 0, 8, st));
+    hipLaunchKernelGGL(k_r1cs_wtns, dim3((r->n_wires + 255) / 256), dim3(256), 0, st, (const uint4*)d_wtns, r->n_wires,
+                       d_n16 ? nullptr : r->d_n16, r->d_mask + r->n_words);
+    if (r->M) {
+        const uint64_t waves = (uint64_t)r->n_slices + r->n_long;
+        {
+            k16_stat_scope sc(ctx, "r1cs_rows", st);
+            hipLaunchKernelGGL(k_r1cs_rows, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, r->d_slices, r->n_slices, r->d_rowof,
+                               r->d_longs, r->n_long, r->d_wire, r->d_coef, d_wtns, d_n16 ? d_n16 : r->d_n16, r->d_rows);
+        }
+        {
+            k16_stat_scope sc(ctx, "r1cs_judge", st);
+            hipLaunchKernelGGL(k_r1cs_judge, dim3((r->M + 255) / 256), dim3(256), 0, st, r->d_rows, r->M, r->n_words, r->d_mask);
+        }
+    }
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(r->h_mask, r->d_mask, ((size_t)r->n_words + 1) * 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+static int r1cs_check(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint16_t* d_n16, uint64_t* n_failed, uint32_t* h_failed,
+                      uint32_t cap)
+{
+    *n_failed      = 0;
+    r->have_values = false;
+    const int rc   = r1cs_enqueue(ctx, r, d_wtns, d_n16);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream); // nothing of the check stays in flight
+        return rc;
+    }
+    const unsigned long long flags = r->h_mask[r->n_words];
+    if (flags) {
+        ctx->err = (flags & WTNS_NOT_BELOW_R) ? "witness: a wire value is not below r" : "witness: wire 0 is not 1";
+        return K16_ERR_FORMAT;
+    }
+    r->have_values = true;
+    uint64_t count = 0;
+    for (uint32_t w = 0; w < r->n_words; w++) {
+        unsigned long long m = r->h_mask[w];
+        while (m) {
+            const uint32_t c = w * 64u + (uint32_t)__builtin_ctzll(m);
+            if (h_failed && count < cap) h_failed[count] = c;
+            count++;
+            m &= m - 1;
+        }
+    }
+    *n_failed = count;
+    return K16_OK;
+}
+
+static int r1cs_check_host(k16_ctx* ctx, k16_r1cs* r, const void* h_wtns, uint64_t* n_failed, uint32_t* h_failed, uint32_t cap)
+{
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    K16_HIP(ctx, hipMemcpyAsync(r->d_wtns, h_wtns, (size_t)r->n_wires * 32, hipMemcpyHostToDevice, ctx->stream));
+    return r1cs_check(ctx, r, r->d_wtns, nullptr, n_failed, h_failed, cap);
+}
+
+extern "C" int k16_r1cs_check_mem(k16_ctx* ctx, k16_r1cs* r, const void* h_wtns, uint64_t n_wires, uint64_t* n_failed,
+                                  uint32_t* h_failed, uint32_t cap)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !r || !h_wtns || !n_failed || r->ctx != ctx) return K16_ERR_ARG;
+    *n_failed = 0;
+    if (n_wires != r->n_wires) {
+        ctx->err = "witness does not have as many values as the circuit has wires";
+        return K16_ERR_ARG;
+    }
+    return r1cs_check_host(ctx, r, h_wtns, n_failed, h_failed, cap);
+    });
+}
+
+extern "C" int k16_r1cs_check_file(k16_ctx* ctx, k16_r1cs* r, const char* wtns_path, uint64_t* n_failed, uint32_t* h_failed,
+                                   uint32_t cap)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !r || !wtns_path || !n_failed || r->ctx != ctx) return K16_ERR_ARG;
+    *n_failed = 0;
+    return k16_wtns_file_apply(ctx, wtns_path, [&](const uint8_t* values, uint64_t have) -> int {
+        if (have != r->n_wires) {
+            ctx->err = "wtns: the file does not hold as many values as the circuit has wires";
+            return K16_ERR_FORMAT;
+        }
+        return r1cs_check_host(ctx, r, values, n_failed, h_failed, cap);
+    });
+    });
+}
+
+extern "C" int k16_r1cs_check_prover_witness(k16_prover* p, k16_r1cs* r, uint64_t* n_failed, uint32_t* h_failed, uint32_t cap)
+{
+    if (!p || !r || !n_failed) return K16_ERR_ARG;
+    *n_failed = 0;
+    return k16_guard(r->ctx, [&]() -> int {
+    k16_ctx*        ctx    = nullptr;
+    const Fr*       d_wtns = nullptr;
+    const uint16_t* d_n16  = nullptr;
+    uint32_t        n_vars = 0;
+    const int       rc     = k16_prover_witness_view(p, &ctx, &d_wtns, &d_n16, &n_vars);
+    if (r->ctx != ctx) {
+        ctx->err = "the R1CS object must live on the prover's context";
+        return K16_ERR_ARG;
+    }
+    if (n_vars != r->n_wires) {
+        ctx->err = "the circuit's wire count is not the proving key's";
+        return K16_ERR_ARG;
+    }
+    if (rc) return rc;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    return r1cs_check(ctx, r, d_wtns, d_n16, n_failed, h_failed, cap);
+    });
+}
+
+extern "C" int k16_r1cs_last_values(k16_r1cs* r, uint32_t constraint, void* h_out96)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !h_out96) return K16_ERR_ARG;
+    k16_ctx* ctx = r->ctx;
+    if (!r->have_values || constraint >= r->M) {
+        ctx->err = r->have_values ? "constraint number out of range" : "no completed check to read values from";
+        return K16_ERR_ARG;
+    }
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    Fr packed[3];
+    for (int m = 0; m < 3; m++)
+        K16_HIP(ctx, hipMemcpyAsync(&packed[m], r->d_rows + (size_t)m * r->M + constraint, 32, hipMemcpyDeviceToHost, ctx->stream));
+    K16_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int m = 0; m < 3; m++) {
+        const Fr v = fr9_to_standard(fr9_load(packed[m].v)); // the same host code the device runs
+        memcpy((uint8_t*)h_out96 + 32 * m, v.v, 32);
+    }
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_r1cs_match_zkey(k16_ctx* ctx, const k16_r1cs* r, const void* zkey, size_t size, uint32_t* mismatch)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx || !r || !zkey || !mismatch) return K16_ERR_ARG;
+    *mismatch = 0;
+    R1csMismatch mm;
+    const char*  why = "";
+    const int    rc  = r1cs_match_zkey(r->file, (const uint8_t*)zkey, size, &mm, &why);
+    if (rc) {
+        ctx->err = *why ? why : "zkey: malformed header or coefficient section";
+        return rc;
+    }
+    *mismatch = mm.kind;
+    if (mm.kind) {
+        static const char* const kinds[] = {"", "header", "matrix A", "matrix B", "public rows"};
+        char                     buf[256];
+        snprintf(buf, sizeof buf, "r1cs / zkey mismatch: %s, constraint %u, wire %u (%s)", kinds[mm.kind], mm.constraint, mm.wire, why);
+        ctx->err = buf;
+    }
+    return K16_OK;
+    });
+}

@@ -46,6 +46,8 @@ SYMBOLS = [
     "k16_verify_batch_folded", "k16_verify_fold_gt",
     "k16_vk_create_from_zkey", "k16_vk_create_from_zkey_file", "k16_prover_set_vk", "k16_prover_prove_mem_verified",
     "k16_prover_prove_compact_verified", "k16_prover_prove_file_verified", "k16_verify_split_gt", "k16_fullprover_set_verify",
+    "k16_r1cs_create", "k16_r1cs_create_mem", "k16_r1cs_destroy", "k16_r1cs_info", "k16_r1cs_check_mem", "k16_r1cs_check_file",
+    "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
     "k16_msm_sharded_last_error", "k16_msm_sharded_set_bases", "k16_msm_sharded_set_bases_device", "k16_msm_sharded_run",
     "k16_msm_sharded_run_device", "k16_msm_sharded_set_piece_rows", "k16_msm_sharded_last_ms",
@@ -158,6 +160,16 @@ def load():
     L.k16_verify_split_gt.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.k16_zkey_check.argtypes = [vp, vp, sz, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
     L.k16_zkey_check_file.argtypes = [vp, C.c_char_p, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(u64)]
+    L.k16_r1cs_create.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
+    L.k16_r1cs_create_mem.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    L.k16_r1cs_destroy.argtypes = [vp]
+    L.k16_r1cs_destroy.restype = None
+    L.k16_r1cs_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
+    L.k16_r1cs_check_mem.argtypes = [vp, vp, vp, u64, C.POINTER(u64), vp, u32]
+    L.k16_r1cs_check_file.argtypes = [vp, vp, C.c_char_p, C.POINTER(u64), vp, u32]
+    L.k16_r1cs_check_prover_witness.argtypes = [vp, vp, C.POINTER(u64), vp, u32]
+    L.k16_r1cs_last_values.argtypes = [vp, u32, vp]
+    L.k16_r1cs_match_zkey.argtypes = [vp, vp, vp, sz, C.POINTER(u32)]
     L.k16_msm_sharded_create.argtypes = [C.POINTER(i32), i32, i32, u64, C.POINTER(vp)]
     L.k16_msm_sharded_destroy.argtypes = [vp]
     L.k16_msm_sharded_destroy.restype = None
@@ -565,6 +577,76 @@ class Prover:
     def close(self):
         if self.h:
             self.ctx.L.k16_prover_destroy(self.h)
+            self.h = None
+
+
+class R1cs:
+    """A circuit's .r1cs file on the device (k16_r1cs_*): which constraints does a witness break?  path_or_bytes: a file
+    name or the file's bytes.  The check methods return (n_failed, ndarray of the lowest min(n_failed, cap) constraint
+    numbers, ascending); cap=None asks for all of them."""
+
+    def __init__(self, ctx, path_or_bytes):
+        self.ctx = ctx
+        h = C.c_void_p()
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            raw = bytes(path_or_bytes)
+            rc = ctx.L.k16_r1cs_create_mem(ctx.h, raw, len(raw), C.byref(h))
+        else:
+            rc = ctx.L.k16_r1cs_create(ctx.h, str(path_or_bytes).encode(), C.byref(h))
+        if rc:
+            raise K16Error(rc, (ctx.L.k16_last_error(ctx.h) or b"").decode())
+        self.h = h
+
+    def info(self):
+        nw, npub, m, nt = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self.ctx._chk(self.ctx.L.k16_r1cs_info(self.h, C.byref(nw), C.byref(npub), C.byref(m), C.byref(nt)))
+        return dict(n_wires=nw.value, n_public=npub.value, n_constraints=m.value, n_terms=nt.value)
+
+    def _check(self, call, cap, err_ctx=None):
+        cap = self.info()["n_constraints"] if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        n = C.c_uint64()
+        rc = call(C.byref(n), _p(out), cap)
+        if rc:
+            c = err_ctx or self.ctx
+            raise K16Error(rc, (c.L.k16_last_error(c.h) or b"").decode())
+        return int(n.value), out[:min(int(n.value), cap)].copy()
+
+    def check(self, wtns, cap=None):
+        """k16_r1cs_check_mem: wtns = n_wires x 32 bytes, standard form."""
+        wtns = np.ascontiguousarray(wtns, dtype=np.uint8)
+        L, c, h = self.ctx.L, self.ctx.h, self.h
+        return self._check(lambda *a: L.k16_r1cs_check_mem(c, h, _p(wtns), wtns.size // 32, *a), cap)
+
+    def check_file(self, path, cap=None):
+        L, c, h = self.ctx.L, self.ctx.h, self.h
+        return self._check(lambda *a: L.k16_r1cs_check_file(c, h, str(path).encode(), *a), cap)
+
+    def check_prover(self, prover, cap=None):
+        """k16_r1cs_check_prover_witness: the witness of prover's last prove call, read in place on the device."""
+        L, h = self.ctx.L, self.h
+        return self._check(lambda *a: L.k16_r1cs_check_prover_witness(prover.h, h, *a), cap, err_ctx=prover.ctx)
+
+    def values(self, i):
+        """(A.w, B.w, C.w) of constraint i as the last check computed them, as ints."""
+        out = np.zeros(96, dtype=np.uint8)
+        self.ctx._chk(self.ctx.L.k16_r1cs_last_values(self.h, int(i), _p(out)))
+        return tuple(int.from_bytes(out[32 * k:32 * k + 32].tobytes(), "little") for k in range(3))
+
+    def match_zkey(self, zkey_bytes):
+        """k16_r1cs_match_zkey: 0 when the zkey was made from this circuit, else 1 header / 2 A / 3 B / 4 public rows
+        (details: last_error())."""
+        zkey_bytes = bytes(zkey_bytes)
+        mm = C.c_uint32()
+        self.ctx._chk(self.ctx.L.k16_r1cs_match_zkey(self.ctx.h, self.h, zkey_bytes, len(zkey_bytes), C.byref(mm)))
+        return int(mm.value)
+
+    def last_error(self):
+        return (self.ctx.L.k16_last_error(self.ctx.h) or b"").decode()
+
+    def close(self):
+        if self.h:
+            self.ctx.L.k16_r1cs_destroy(self.h)
             self.h = None
 
 
