@@ -562,6 +562,35 @@ int  k16_r1cs_last_values(k16_r1cs* r, uint32_t constraint, void* h_out96);
  * 4 public rows -- with its constraint and wire in k16_last_error.  K16_ERR_FORMAT / K16_ERR_CURVE for an unreadable zkey. */
 int  k16_r1cs_match_zkey(k16_ctx* ctx, const k16_r1cs* r, const void* zkey, size_t size, uint32_t* mismatch);
 
+/* ---- set-up from a trapdoor: a valid proving key for any .r1cs, made on the GPU ----
+ * WARNING: the key is DEVELOPMENT AND TEST MATERIAL.  Whoever holds the trapdoor can forge proofs.  A key whose trapdoor was
+ * passed in, or drawn here and held in this process's memory, must never guard anything of value: production keys come from a
+ * multi-party ceremony in which nobody ever knows tau, alpha, beta, gamma or delta.
+ * k16_r1cs_setup* evaluate the circuit's QAP at tau on the device and write the snarkjs Groth16 zkey the prover reads (sections
+ * 1 .. 10 in order; formulas and layout: csrc/setup_plan.h).  Section 10 carries a zero circuit hash and no
+ * contribution; nothing in this project can test whether snarkjs itself loads the file.
+ * trapdoor160: tau | alpha | beta | gamma | delta, 5 x 32 B little-endian standard form, each in [1, r).  NULL: the five values
+ * are drawn from the OS CSPRNG the way a proof's r and s are.
+ *   k16_r1cs_setup_size  the exact size of the key in bytes
+ *   k16_r1cs_setup       into out_zkey[0 .. cap); *out_size = the key's size, also when K16_ERR_BUFFER says that cap is too small
+ *   k16_r1cs_setup_file  into a file, written under a temporary name and renamed: an error leaves no partial file behind
+ * K16_ERR_ARG: a trapdoor value of 0 or >= r; tau with tau^(2N) = 1 (tau lies in the evaluation domain or in its odd coset: a
+ * Lagrange denominator or Z(tau) vanishes); a circuit with 0 constraints; an R1CS object of another context; 3 * nWires >= 2^32;
+ * a domain above 2^27.  K16_ERR_IO: the file cannot be written, or the OS gives no random bytes.
+ * k16_generator_mul: d_out[i] = scalar_i * G, the contract and the bytes of k16_synth_points_scalars (any 256-bit scalar, 32 B
+ * little-endian standard form, on the device; affine Montgomery out, the all-zero point for a multiple of r), through a window
+ * table of the generator that is built on the device on first use and freed with the context: ceil(256 / w) complete mixed
+ * additions per point instead of a double-and-add walk, and one inversion per batch of points.  k16_generator_mul_info: w and
+ * the number of windows of a group (K16_G1 / K16_G2).
+ * THREADING: as k16_r1cs_check_*: one call at a time per object, on the context's stream, under the context's one-caller rule.
+ * k16_r1cs_setup* return when the key is complete; k16_generator_mul enqueues (k16_sync waits).  Every error leaves nothing in
+ * flight. */
+int k16_r1cs_setup_size(const k16_r1cs* r, uint64_t* zkey_bytes);
+int k16_r1cs_setup(k16_ctx* ctx, k16_r1cs* r, const uint8_t* trapdoor160, void* out_zkey, size_t cap, size_t* out_size);
+int k16_r1cs_setup_file(k16_ctx* ctx, k16_r1cs* r, const uint8_t* trapdoor160, const char* zkey_path);
+int k16_generator_mul(k16_ctx* ctx, int group, const void* d_scalars, uint64_t n, void* d_out_affine);
+int k16_generator_mul_info(int group, unsigned* window_bits, unsigned* n_windows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,11 @@ struct k16_ctx {
     // the per-window combine of an MSM's partial sums runs on the host pool only when asked to (the prover does for the H MSM,
     // the last item on a proof's critical path; for MSMs whose combine overlaps GPU work, waking the pool only costs)
     bool                              parallel_combine = false;
+
+    // k16_generator_mul (setup.hip): the window table of the group's generator, built on the device on first use --
+    // entry (k, d) = d * 2^(w k) * G as packed R' coordinates -- and the scratch area of the batched affine conversion
+    void*      gen_table[2] = {nullptr, nullptr};
+    k16_devbuf gen_scratch;
 };
 // Scalar classes of one scalar vector (msm_classes.hip; include/k16.h k16_scalar_classes_*): per mask set and bit b < 8 the
 // list of wires whose scalar is below 256, has bit b set and whose table row is not (0,0); the scalars of 256 and above
@@ -306,6 +311,13 @@ int k16_wtns_file_apply(k16_ctx* ctx, const char* wtns_path, const std::function
 // K16_ERR_ARG (with the context's error text) unless that call succeeded -- plain or compact upload alike; a failed or
 // aborted prove leaves the buffers incomplete.
 int k16_prover_witness_view(k16_prover* p, k16_ctx** ctx, const k16::Fr** d_wtns, const uint16_t** d_n16, uint32_t* n_vars);
+
+// host-side helpers for setup.hip
+// 32 random bytes below r from the OS CSPRNG, the way a proof's r and s are drawn (prover.hip)
+int k16_random_scalar(uint8_t out[32]);
+namespace k16 { struct R1csFile; }
+// the context and the parsed circuit of an R1CS object (r1cs_check.hip)
+void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const k16::R1csFile** file);
 
 // host-side helpers implemented in ntt.hip
 int k16_ntt_get_table(k16_ctx* ctx, uint64_t max_domain, k16_ntt_table** out);

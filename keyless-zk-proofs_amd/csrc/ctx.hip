@@ -144,6 +144,9 @@ extern "C" void k16_ctx_destroy(k16_ctx* c)
         if (kv.second.roots9) (void)hipFree(kv.second.roots9);
     for (auto& kv : c->ntt_tables)
         if (kv.second.stage9) (void)hipFree(kv.second.stage9);
+    for (void* t : c->gen_table)
+        if (t) (void)hipFree(t);
+    if (c->gen_scratch.p) (void)hipFree(c->gen_scratch.p);
     for (hipStream_t ph : c->placeholder_streams) (void)hipStreamDestroy(ph);
     if (c->pinned) (void)hipHostFree(c->pinned);
     for (int i = 0; i < k16_ctx::PEND_SLOTS; i++)

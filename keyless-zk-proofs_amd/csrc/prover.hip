@@ -1648,6 +1648,8 @@ extern "C" int k16_vk_create_from_zkey_file(k16_ctx* ctx, const char* zkey_path,
 }
 
 // a file mapped read-only for the duration of fn (ctx.h)
+int k16_random_scalar(uint8_t out[32]) { return sample_blinding(out); }
+
 int k16_file_apply(k16_ctx* ctx, const char* path, const char* what, const std::function<int(const uint8_t*, size_t)>& fn)
 {
     MappedFile mf;

@@ -100,6 +100,12 @@ struct k16_r1cs {
     bool                have_values = false; // d_rows holds the sums of a completed check (k16_r1cs_last_values)
 };
 
+void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const R1csFile** file)
+{
+    *ctx  = r->ctx;
+    *file = &r->file;
+}
+
 static void r1cs_free(k16_r1cs* r)
 {
     if (!r) return;

@@ -48,6 +48,7 @@ SYMBOLS = [
     "k16_prover_prove_compact_verified", "k16_prover_prove_file_verified", "k16_verify_split_gt", "k16_fullprover_set_verify",
     "k16_r1cs_create", "k16_r1cs_create_mem", "k16_r1cs_destroy", "k16_r1cs_info", "k16_r1cs_check_mem", "k16_r1cs_check_file",
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
+    "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
     "k16_msm_sharded_last_error", "k16_msm_sharded_set_bases", "k16_msm_sharded_set_bases_device", "k16_msm_sharded_run",
     "k16_msm_sharded_run_device", "k16_msm_sharded_set_piece_rows", "k16_msm_sharded_last_ms",
@@ -170,6 +171,11 @@ def load():
     L.k16_r1cs_check_prover_witness.argtypes = [vp, vp, C.POINTER(u64), vp, u32]
     L.k16_r1cs_last_values.argtypes = [vp, u32, vp]
     L.k16_r1cs_match_zkey.argtypes = [vp, vp, vp, sz, C.POINTER(u32)]
+    L.k16_r1cs_setup_size.argtypes = [vp, C.POINTER(u64)]
+    L.k16_r1cs_setup.argtypes = [vp, vp, vp, vp, sz, C.POINTER(sz)]
+    L.k16_r1cs_setup_file.argtypes = [vp, vp, vp, C.c_char_p]
+    L.k16_generator_mul.argtypes = [vp, i32, vp, u64, vp]
+    L.k16_generator_mul_info.argtypes = [i32, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.k16_msm_sharded_create.argtypes = [C.POINTER(i32), i32, i32, u64, C.POINTER(vp)]
     L.k16_msm_sharded_destroy.argtypes = [vp]
     L.k16_msm_sharded_destroy.restype = None
@@ -406,6 +412,33 @@ class Context:
         self.sync()
         return d
 
+    def generator_mul(self, group, scalars):
+        """k16_generator_mul: scalars = list of ints below 2^256 (NOT reduced: any 256-bit value is legal), or an (n, 32) uint8
+        array of little-endian values -> uint8 array (n, AFF_BYTES) of scalar_i * G through the generator's window table."""
+        return self._scalar_points(self.L.k16_generator_mul, group, scalars)
+
+    def synth_points_scalars_raw(self, group, scalars):
+        """k16_synth_points_scalars on the scalars as they are (generator_mul's argument forms)."""
+        return self._scalar_points(self.L.k16_synth_points_scalars, group, scalars)
+
+    def _scalar_points(self, call, group, scalars):
+        if isinstance(scalars, np.ndarray):
+            buf = np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1)
+        else:
+            buf = np.frombuffer(b"".join(int(k).to_bytes(32, "little") for k in scalars), dtype=np.uint8)
+        n = buf.size // 32
+        if n == 0:
+            return np.zeros((0, AFF_BYTES[group]), dtype=np.uint8)
+        d_s = self.to_device(buf)
+        d_o = self.alloc(n * AFF_BYTES[group])
+        try:
+            self._chk(call(self.h, group, d_s.ptr, n, d_o.ptr))
+            self.sync()
+            return d_o.download(np.uint8, (n, AFF_BYTES[group])).copy()
+        finally:
+            d_s.free()
+            d_o.free()
+
     def synth_points_scalars(self, group, scalars):
         """scalars: list of ints (any size, reduced mod r here) -> uint8 array (n, AFF_BYTES) of scalar_i * G."""
         R_MOD = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
@@ -641,6 +674,36 @@ class R1cs:
         self.ctx._chk(self.ctx.L.k16_r1cs_match_zkey(self.ctx.h, self.h, zkey_bytes, len(zkey_bytes), C.byref(mm)))
         return int(mm.value)
 
+    def setup_size(self):
+        """k16_r1cs_setup_size: the exact size in bytes of the key setup() makes."""
+        n = C.c_uint64()
+        self.ctx._chk(self.ctx.L.k16_r1cs_setup_size(self.h, C.byref(n)))
+        return int(n.value)
+
+    @staticmethod
+    def _trapdoor(trapdoor):
+        if trapdoor is None:
+            return None
+        if isinstance(trapdoor, (bytes, bytearray)):
+            assert len(trapdoor) == 160
+            return bytes(trapdoor)
+        assert len(trapdoor) == 5
+        return b"".join(int(x).to_bytes(32, "little") for x in trapdoor)
+
+    def setup(self, trapdoor=None, ctx=None):
+        """k16_r1cs_setup: a Groth16 zkey for this circuit as bytes.  trapdoor: (tau, alpha, beta, gamma, delta) as ints in [1, r)
+        or 160 bytes; None draws them from the OS.  DEVELOPMENT AND TEST MATERIAL: whoever holds the trapdoor can forge proofs."""
+        ctx = ctx or self.ctx
+        out = np.empty(self.setup_size(), dtype=np.uint8)
+        n = C.c_size_t()
+        ctx._chk(ctx.L.k16_r1cs_setup(ctx.h, self.h, self._trapdoor(trapdoor), _p(out), out.size, C.byref(n)))
+        assert n.value == out.size
+        return out.tobytes()
+
+    def setup_file(self, path, trapdoor=None):
+        """k16_r1cs_setup_file: the same key, written to path."""
+        self.ctx._chk(self.ctx.L.k16_r1cs_setup_file(self.ctx.h, self.h, self._trapdoor(trapdoor), str(path).encode()))
+
     def last_error(self):
         return (self.ctx.L.k16_last_error(self.ctx.h) or b"").decode()
 
@@ -648,6 +711,15 @@ class R1cs:
         if self.h:
             self.ctx.L.k16_r1cs_destroy(self.h)
             self.h = None
+
+
+def generator_mul_info(group):
+    """k16_generator_mul_info: (window bits, number of windows) of a group's generator table."""
+    w, nw = C.c_uint(), C.c_uint()
+    rc = load().k16_generator_mul_info(group, C.byref(w), C.byref(nw))
+    if rc:
+        raise K16Error(rc)
+    return int(w.value), int(nw.value)
 
 
 def _zkey_n_public(head):
