@@ -307,6 +307,18 @@ int k16_synth_points_scalars(k16_ctx* ctx, int group, const void* d_scalars, uin
 /* ---- batch primitives, for parity tests of the device arithmetic ---- */
 int k16_field_op_vec(k16_ctx* ctx, int field, int op, const void* h_a, const void* h_b, void* h_r, uint64_t n);
 int k16_point_op_vec(k16_ctx* ctx, int group, int op, const void* h_p1, const void* h_p2, void* h_r, uint64_t n);
+/* A TEST PRIMITIVE, not part of the service's interface: runs a caller's program through the wave-cooperative verifier's
+ * interpreter -- the kernel k16_verify_batch_folded launches for its final exponentiation, unchanged -- one block per set
+ * of 12 inputs.  Program format: csrc/verify_script.h (CoopProgram: a class per step, 64 instruction words per step, term
+ * words of the linear steps); slots [0, n_const) are constants, given as n_const x 9 raw radix-2^29 limbs in the R' = 2^261
+ * domain (slot 0 = 0, slot 1 = R' mod p; any representative below 5p elsewhere), slots [n_const, n_const + 12) the inputs
+ * (h_inputs: n x 12 x 32 B canonical Montgomery Fq), and h_out receives the 12 slots out_slot names, canonical (n x 12 x
+ * 32 B).  Every argument is validated on the host before anything is launched: K16_ERR_ARG names the rule that failed
+ * (k16_last_error).  Not for concurrent use with k16_vk_create or a folded verification on another thread (it adjusts the
+ * kernel's dynamic-LDS attribute, which the process shares).  tests/coop_asm.py assembles such programs; tests/test_gpu_coop_exec.py uses them. */
+int k16_coop_exec(k16_ctx* ctx, const uint8_t* step_class, uint64_t n_steps, const uint64_t* words /* 64 per step */,
+                  const uint32_t* terms, uint64_t n_terms, uint32_t n_const, uint32_t n_slots, const uint32_t* out_slot /* [12] */,
+                  const uint32_t* const9, const void* h_inputs, uint64_t n, void* h_out);
 
 /* ---- Groth16 prover (groth16.cpp:41-360 behind fullprover.cpp:136-250) ----
  * k16_prover_create parses the zkey (iden3 binfile, sections 1,2,4-9), checks r, and uploads

@@ -433,8 +433,10 @@ __global__ void __launch_bounds__(128) k_verify_coop(CoopDev D, const uint32_t* 
                     }
                 }
                 // the quotient by p, estimated from the two top accumulators (lane g = 2 holds limbs 6, 7, 8; p / 2^232 =
-                // 3171406.3; 2^44 / 3171407 = 5547122.9) and taken low: the result is non-negative and below 5p -- fine
-                // for fmul9, whose operand bounds may multiply to 128
+                // 3171406.45; 5547123 = floor(2^44 / 3171407): the estimate errs low) and taken low: the result is non-negative
+                // and below 5p -- fine for fmul9, whose operand bounds may multiply to 128.  Rigorously, for operands below 5p
+                // and sum |cf| <= COOP_MAX_COEF: 2p < result < 3.015p, top_est < 2^37.3, q <= 53247 (the derivation heads
+                // tests/cpp/coop_bounds_check.cpp, which evaluates these bounds on the programs that run)
                 const uint64_t top_est = (uint64_t)(a3[2] + (a3[1] >> 29));                       // < 2^38
                 int64_t        q       = (int64_t)(((top_est >> 11) * 5547123ull) >> 33) - 2;      // floor(top / 3171407) - 2 .. - 4
                 q                      = q < 0 ? 0 : q;
@@ -1608,6 +1610,91 @@ extern "C" int k16_verify_fold_gt(k16_ctx* ctx, const k16_vk* vk, const void* h_
             return K16_ERR_ARG;
         }
     memcpy(h_out_gt, &v, sizeof v);
+    return K16_OK;
+    });
+}
+
+// parity tests of the interpreter itself: a CALLER's program through k_verify_coop<false, COOP_FOLD> -- the instantiation the
+// fold launches, unchanged -- one block per set of 12 inputs.  Everything is validated on the host (coop_program_check,
+// coop_consts_check, the LDS need of coop_layout, the grid) BEFORE anything is allocated or launched: a malformed program is
+// K16_ERR_ARG with the reason in k16_last_error.  The constants are uploaded as given (raw limbs), so a test can place any
+// representative of a residue below the linear step's operand bound into a slot.
+extern "C" int k16_coop_exec(k16_ctx* ctx, const uint8_t* step_class, uint64_t n_steps, const uint64_t* words, const uint32_t* terms,
+                             uint64_t n_terms, uint32_t n_const, uint32_t n_slots, const uint32_t* out_slot, const uint32_t* const9,
+                             const void* h_inputs, uint64_t n, void* h_out)
+{
+    return k16_guard(ctx, [&]() -> int {
+    if (!ctx) return K16_ERR_ARG;
+    auto bad = [&](const std::string& m) {
+        ctx->err = "k16_coop_exec: " + m;
+        return (int)K16_ERR_ARG;
+    };
+    if (!step_class || !words || !terms || !out_slot || !const9 || !h_inputs || !h_out) return bad("null argument");
+    if (!n || n > (1u << 16)) return bad("1 .. 65536 input sets");
+    if (!n_steps || n_steps >= (1u << 20) || !n_terms || n_terms >= (1u << 24)) return bad("1 .. 2^20 - 1 steps, 1 .. 2^24 - 1 terms");
+    if (n_const >= (1u << 14) || n_slots >= (1u << 14)) return bad("slot numbers have 14 bits");
+    CoopProgram P;
+    P.n_const = P.in_base = n_const;
+    P.n_slots = n_slots;
+    for (int i = 0; i < 12; i++) P.out_slot[i] = out_slot[i];
+    P.step_class.assign(step_class, step_class + n_steps);
+    P.words.assign(words, words + n_steps * 64);
+    P.terms.assign(terms, terms + n_terms);
+    std::string why;
+    if (!coop_program_check(P, &why, COOP_FE_INPUTS) || !coop_consts_check(const9, n_const, &why)) return bad(why);
+    CoopLayout L;
+    coop_layout(&P, &L);
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    hipFuncAttributes fa{};
+    const void*       fn         = (const void*)k_verify_coop<false, COOP_FOLD>;
+    const size_t      static_lds = hipFuncGetAttributes(&fa, fn) == hipSuccess ? fa.sharedSizeBytes : 4096;
+    const size_t      lds_max    = 160 * 1024 - static_lds;
+    if (L.lds_bytes > lds_max) return bad("the program needs " + std::to_string(L.lds_bytes) + " bytes of LDS (slot file + two staging halves); " + std::to_string(lds_max) + " are there");
+    // (the attribute belongs to the function, i.e. to the whole process, and k16_vk_create sets it to the fold's own need: the
+    // largest value serves both, but a call here must not run concurrently with k16_vk_create or a fold on another thread --
+    // this is a test primitive, single-threaded by contract)
+    K16_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+    hipStream_t st = ctx->stream;
+    DevBufs     tmp;
+    uint64_t*   d_words = nullptr;
+    uint32_t *  d_terms = nullptr, *d_hdr = nullptr, *d_chunks = nullptr, *d_c9 = nullptr;
+    uint8_t *   d_in = nullptr, *d_st = nullptr;
+    Fq *        d_out = nullptr, *d_target = nullptr;
+    std::vector<uint32_t> c9(((size_t)n_const * 9 + 3) & ~(size_t)3, 0u); // (the prologue copies whole uint4s)
+    memcpy(c9.data(), const9, (size_t)n_const * 36);
+    K16_HIP(ctx, tmp.alloc((void**)&d_words, P.words.size() * 8));
+    K16_HIP(ctx, tmp.alloc((void**)&d_terms, P.terms.size() * 4));
+    K16_HIP(ctx, tmp.alloc((void**)&d_hdr, L.hdr.size() * 4));
+    K16_HIP(ctx, tmp.alloc((void**)&d_chunks, L.chunks.size() * 4));
+    K16_HIP(ctx, tmp.alloc((void**)&d_c9, c9.size() * 4));
+    K16_HIP(ctx, tmp.alloc((void**)&d_in, (size_t)n * 12 * sizeof(Fq)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_out, (size_t)n * 12 * sizeof(Fq)));
+    K16_HIP(ctx, tmp.alloc((void**)&d_target, 12 * sizeof(Fq))); // the kernel compares with a target and writes a flag:
+    K16_HIP(ctx, tmp.alloc((void**)&d_st, n));                   // neither is read here
+    K16_HIP(ctx, hipMemsetAsync(d_target, 0, 12 * sizeof(Fq), st));
+    K16_HIP(ctx, hipMemcpyAsync(d_words, P.words.data(), P.words.size() * 8, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_terms, P.terms.data(), P.terms.size() * 4, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_hdr, L.hdr.data(), L.hdr.size() * 4, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_chunks, L.chunks.data(), L.chunks.size() * 4, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_c9, c9.data(), c9.size() * 4, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_in, h_inputs, (size_t)n * 12 * sizeof(Fq), hipMemcpyHostToDevice, st));
+    CoopDev D;
+    D.words = d_words;
+    D.terms = d_terms;
+    D.hdr = d_hdr;
+    D.chunks = d_chunks;
+    D.n_chunks = L.n_chunks;
+    D.chunk_words = L.chunk_words;
+    D.n_const = D.in_base = n_const;
+    D.n_slots = n_slots;
+    D.target_const = 0;
+    for (int i = 0; i < 12; i++) D.out_slot[i] = out_slot[i];
+    hipLaunchKernelGGL((k_verify_coop<false, COOP_FOLD>), dim3((unsigned)n), dim3(128), L.lds_bytes, st, D, d_c9, (const G1Aff*)nullptr,
+                       (const G1Aff*)nullptr, 0u, d_in, (const uint8_t*)nullptr, d_target, d_st, d_out, (uint64_t*)nullptr,
+                       (const Fq2*)nullptr);
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * 12 * sizeof(Fq), hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
     return K16_OK;
     });
 }

@@ -25,9 +25,12 @@
 #include <map>
 #include <stdexcept>
 #include <stdint.h>
+#include <string>
 #include <unordered_map>
 #include <vector>
 #include "bn254_pairing.h"
+#include "bn254_curve.h"
+#include "bn254_fq9.h"
 
 namespace k16t {
 
@@ -887,6 +890,105 @@ inline void coop_run_host(const CoopProgram& P, std::vector<Fq>& slots /* consta
         for (int l = 0; l < 64; l++)
             if (val[l]) slots[P.words[s * 64 + l] & 0x3fff] = res[l];
     }
+}
+
+// ------------------------------------------------------------------------------------------------ program validation
+// What k_verify_coop takes for granted about a program, checked on the host (k16_coop_exec runs a CALLER's program through the
+// kernel: nothing malformed may reach the GPU; tests/cpp/coop_bounds_check.cpp runs it on the four programs built above).
+// n_inputs: the slots from in_base the prologue stores (12 for the FOLD prologue, which k16_coop_exec uses).
+inline bool coop_program_check(const CoopProgram& P, std::string* why, uint32_t n_inputs = 12)
+{
+    auto fail = [&](const std::string& m) {
+        if (why) *why = m;
+        return false;
+    };
+    auto at = [](size_t s, int l) { return " (step " + std::to_string(s) + ", lane " + std::to_string(l) + ")"; };
+    const size_t n_steps = P.step_class.size(), n_terms = P.terms.size();
+    if (!n_steps || n_steps >= (1u << 20)) return fail("program: 1 .. 2^20 - 1 steps");
+    if (P.words.size() != n_steps * 64) return fail("program: 64 words per step");
+    if (n_terms >= (1u << 24)) return fail("program: term offsets have 24 bits");
+    if (P.n_const < 2 || P.in_base != P.n_const) return fail("program: the inputs follow the constants, and slots 0 / 1 are the constants zero / one");
+    if (P.n_slots >= (1u << 14)) return fail("program: slot numbers have 14 bits");
+    if (P.n_slots < P.in_base + n_inputs) return fail("program: the slot file ends inside the input slots");
+    const uint32_t first_dst = P.in_base + n_inputs;
+    for (int i = 0; i < 12; i++)
+        if (P.out_slot[i] >= P.n_slots) return fail("program: output slot " + std::to_string(i) + " outside the slot file");
+    std::vector<uint32_t> written(P.n_slots, 0xffffffffu); // step that wrote the slot last
+    for (size_t s = 0; s < n_steps; s++) {
+        const uint8_t cls = P.step_class[s];
+        if (cls != CS_MUL && cls != CS_LIN && cls != CS_INV) return fail("program: unknown class of step " + std::to_string(s));
+        for (int l = 0; l < 64; l++) {
+            const uint64_t w = P.words[s * 64 + l];
+            if (!(w >> 63)) continue;
+            const uint32_t dst = (uint32_t)(w & 0x3fff), a = (uint32_t)((w >> 14) & 0x3fff), b = (uint32_t)((w >> 28) & 0x3fff);
+            if (dst >= P.n_slots) return fail("destination outside the slot file" + at(s, l));
+            if (dst < first_dst) return fail("destination is a constant or input slot" + at(s, l));
+            if (cls == CS_MUL && (a >= P.n_slots || b >= P.n_slots)) return fail("MUL operand outside the slot file" + at(s, l));
+            if (cls == CS_INV && a >= P.n_slots) return fail("INV operand outside the slot file" + at(s, l));
+            if (cls == CS_LIN) {
+                const int l16 = l & 15;
+                if (l16 == 15) return fail("LIN: lane 15 of a row must stay idle" + at(s, l));
+                const int l0 = l - l16 % 3;
+                if (P.words[s * 64 + l0] != w || P.words[s * 64 + l0 + 1] != w || P.words[s * 64 + l0 + 2] != w)
+                    return fail("LIN: the three lanes of a group must hold the same word" + at(s, l));
+                if (l != l0) continue; // the group is checked at its first lane
+                const uint32_t nt = (uint32_t)((w >> 14) & 0x3f), t0 = (uint32_t)((w >> 20) & 0xffffff);
+                const uint32_t ntp = (nt + COOP_TRIP - 1) & ~(COOP_TRIP - 1);
+                if (nt < 1 || ntp > 63) return fail("LIN: 1 .. 56 terms" + at(s, l));
+                if (t0 % COOP_TRIP) return fail("LIN: a term list starts at a multiple of COOP_TRIP" + at(s, l));
+                if ((size_t)t0 + ntp > n_terms) return fail("LIN: the (padded) term list runs past the term array" + at(s, l));
+                int64_t sum = 0;
+                for (uint32_t k = 0; k < ntp; k++) {
+                    const uint32_t tw = P.terms[t0 + k];
+                    if (k >= nt) {
+                        if (tw != 0) return fail("LIN: padding terms must be 0 x slot 0" + at(s, l));
+                        continue;
+                    }
+                    if ((tw & 0xffff) >= P.n_slots) return fail("LIN: term slot outside the slot file" + at(s, l));
+                    const int32_t cf = (int16_t)(tw >> 16);
+                    sum += cf < 0 ? -cf : cf;
+                }
+                if (sum > COOP_MAX_COEF) return fail("LIN: sum of |coefficients| above COOP_MAX_COEF" + at(s, l));
+            }
+            if (cls != CS_LIN || (l & 15) % 3 == 0) {
+                if (written[dst] == (uint32_t)s) return fail("two lanes of a step write the same slot" + at(s, l));
+                written[dst] = (uint32_t)s;
+            }
+        }
+    }
+    return true;
+}
+
+// The constant slots as raw radix-2^29 limbs (n_const x 9): normalised, below the linear step's operand bound 5p (any
+// representative of a residue below it is allowed), slot 0 = 0 and slot 1 = R' mod p exactly.
+inline bool coop_consts_check(const uint32_t* c9, uint32_t n_const, std::string* why)
+{
+    auto fail = [&](const std::string& m) {
+        if (why) *why = m;
+        return false;
+    };
+    if (!c9 || n_const < 2) return fail("constants: at least zero and one");
+    uint32_t p5[9], c = 0;
+    for (int k = 0; k < 9; k++) {
+        const uint64_t t = (uint64_t)Fq9C::P[k] * 5 + c;
+        p5[k]            = k < 8 ? (uint32_t)(t & Fq9C::MASK) : (uint32_t)t;
+        c                = (uint32_t)(t >> 29);
+    }
+    for (uint32_t i = 0; i < n_const; i++) {
+        const uint32_t* v = c9 + (size_t)i * 9;
+        for (int k = 0; k < 8; k++)
+            if (v[k] >> 29) return fail("constant " + std::to_string(i) + ": limb " + std::to_string(k) + " is not below 2^29");
+        bool below = false;
+        for (int k = 8; k >= 0; k--)
+            if (v[k] != p5[k]) {
+                below = v[k] < p5[k];
+                break;
+            }
+        if (!below) return fail("constant " + std::to_string(i) + " is not below 5p, the linear step's operand bound");
+    }
+    for (int k = 0; k < 9; k++)
+        if (c9[k] != 0 || c9[9 + k] != Fq9C::ONE[k]) return fail("constants: slot 0 must hold 0 and slot 1 the Montgomery one");
+    return true;
 }
 
 } // namespace k16

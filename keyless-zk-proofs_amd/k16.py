@@ -38,7 +38,7 @@ SYMBOLS = [
     "k16_timer_start", "k16_timer_stop", "k16_kernel_stats_enable", "k16_kernel_stats_reset", "k16_kernel_stats_get",
     "k16_ctx_set_option", "k16_msm", "k16_msm_host", "k16_msm_enqueue", "k16_msm_finish", "k16_msm_finish_group", "k16_msm_pending", "k16_msm_abort_all", "k16_msm_bases_prepare", "k16_msm_enqueue_prepared", "k16_msm_fixed_base_info", "k16_msm_fixed_base_prepare", "k16_msm_enqueue_fixed_base", "k16_msm_set_window_bits", "k16_msm_set_lane", "k16_points_sum",
     "k16_msm_zero_row_mask", "k16_msm_set_zero_row_mask", "k16_msm_sort_from_lane", "k16_scalar_classes_create", "k16_scalar_classes_destroy", "k16_scalar_classes_build", "k16_scalar_classes_counts", "k16_msm_enqueue_classified",
-    "k16_ntt", "k16_ntt_host", "k16_synth_points", "k16_synth_points_scalars", "k16_field_op_vec", "k16_point_op_vec",
+    "k16_ntt", "k16_ntt_host", "k16_synth_points", "k16_synth_points_scalars", "k16_field_op_vec", "k16_point_op_vec", "k16_coop_exec",
     "k16_prover_create", "k16_prover_create_mem", "k16_prover_create_shared", "k16_prover_destroy", "k16_prover_info",
     "k16_prover_prove_file", "k16_prover_prove_file_timed", "k16_prover_prove_mem", "k16_prover_compact_buffers", "k16_prover_prove_compact", "k16_fullprover_prove_mem", "k16_fullprover_compact_lease", "k16_fullprover_prove_compact", "k16_fullprover_compact_cancel", "k16_prover_last_h", "k16_prover_warmup_status",
     "k16_vk_create", "k16_vk_destroy", "k16_verify_batch", "k16_verify_coop_gt", "k16_pairing_vec",
@@ -124,6 +124,7 @@ def load():
     L.k16_synth_points_scalars.argtypes = [vp, i32, vp, u64, vp]
     L.k16_field_op_vec.argtypes = [vp, i32, i32, vp, vp, vp, u64]
     L.k16_point_op_vec.argtypes = [vp, i32, i32, vp, vp, vp, u64]
+    L.k16_coop_exec.argtypes = [vp, vp, u64, vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp, u64, vp]
     L.k16_prover_create.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
     L.k16_prover_create_mem.argtypes = [vp, vp, sz, C.POINTER(vp)]
     L.k16_prover_create_shared.argtypes = [vp, vp, C.POINTER(vp)]
@@ -474,6 +475,24 @@ class Context:
         r = np.zeros_like(a)              # (n, 4) u64; (n, 8) for FQ2N elements
         self._chk(self.L.k16_field_op_vec(self.h, field, op, _p(a), _p(b), _p(r), n))
         return r
+
+    def coop_exec(self, step_class, words, terms, n_const, n_slots, out_slot, const9, inputs):
+        """k16_coop_exec (a test primitive): a caller's program through the wave-cooperative verifier's interpreter.
+        step_class: uint8[n_steps]; words: uint64[n_steps * 64]; terms: uint32[]; const9: uint32[n_const, 9] raw limbs;
+        inputs: uint8[n, 12, 32] canonical Montgomery Fq.  Returns uint8[n, 12, 32].  Raises K16Error(ARG) with the rule
+        a malformed program breaks; nothing is launched then."""
+        sc = np.ascontiguousarray(step_class, dtype=np.uint8)
+        w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+        t = np.ascontiguousarray(terms, dtype=np.uint32).reshape(-1)
+        c9 = np.ascontiguousarray(const9, dtype=np.uint32).reshape(-1)
+        os_ = np.ascontiguousarray(out_slot, dtype=np.uint32).reshape(-1)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint8).reshape(-1, 12, 32)
+        if w.size != 64 * sc.size or os_.size != 12 or c9.size != 9 * int(n_const):
+            raise K16Error(-3, "coop_exec: array sizes")
+        out = np.zeros_like(inp)
+        self._chk(self.L.k16_coop_exec(self.h, _p(sc), sc.size, _p(w), _p(t), t.size, int(n_const), int(n_slots), _p(os_), _p(c9),
+                                       _p(inp), inp.shape[0], _p(out)))
+        return out
 
     def point_op_vec(self, group, op, p1, p2=None):
         p1 = np.ascontiguousarray(p1, dtype=np.uint8)
