@@ -574,6 +574,39 @@ int  k16_r1cs_last_values(k16_r1cs* r, uint32_t constraint, void* h_out96);
  * 4 public rows -- with its constraint and wire in k16_last_error.  K16_ERR_FORMAT / K16_ERR_CURVE for an unreadable zkey. */
 int  k16_r1cs_match_zkey(k16_ctx* ctx, const k16_r1cs* r, const void* zkey, size_t size, uint32_t* mismatch);
 
+/* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
+ * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
+ * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of
+ * public wires the key's nPublic; k16_r1cs_match_zkey is the caller's to run.  From then on EVERY prove call (_mem, _compact,
+ * _file, _file_timed and their _verified forms) runs the check of k16_r1cs_check_* on its own witness where it lies on the device,
+ * on a stream the prover already has, behind the proof's last kernels (no stream is created); the call joins it before it
+ * returns, on every path.  JSON, return value, *out_ok and out_proof are what they are without a circuit: a proof is still written for a
+ * broken witness, the caller decides.  While attached, the object's per-check buffers are the prover's: no other check on it
+ * while a prove call runs.  A prover without a circuit executes nothing of this.
+ * k16_prover_last_check reports the check of the LAST prove call: *status = K16_CHECK_NONE after a call that failed, with
+ * nothing attached, after attaching or detaching, or after the create-time warm-up; K16_CHECK_SATISFIED; K16_CHECK_BROKEN with the exact
+ * *n_failed and, in h_failed (may be NULL), the lowest min(*n_failed, cap, K16_R1CS_REPORT_MAX) constraint numbers, ascending,
+ * the same on every run; K16_CHECK_WITNESS_REFUSED where k16_r1cs_check_* answer K16_ERR_FORMAT (a value >= r, wire 0 != 1).
+ * After SATISFIED or BROKEN, k16_r1cs_last_values on the attached object reads the sums of that call's witness; for more
+ * than K16_R1CS_REPORT_MAX numbers call k16_r1cs_check_prover_witness. */
+#define K16_R1CS_REPORT_MAX 64
+enum { K16_CHECK_NONE = 0, K16_CHECK_SATISFIED = 1, K16_CHECK_BROKEN = 2, K16_CHECK_WITNESS_REFUSED = 3 };
+int  k16_prover_set_r1cs(k16_prover* p, k16_r1cs* r);
+int  k16_prover_last_check(const k16_prover* p, int* status, uint64_t* n_failed, uint32_t* h_failed, uint32_t cap);
+/* Checked proving behind the drop-in FullProver.  r1cs_path: every pool slot parses the file into an R1CS object on its own
+ * context and attaches it (a slot rebuilt after a device fault gets it again); NULL detaches.  The circuit is compared with the
+ * zkey once (k16_r1cs_match_zkey): K16_ERR_FORMAT on a mismatch or an unreadable file, with the reason on stderr and nothing
+ * attached -- the provers keep working unchecked.  K16_ERR_ARG while a slot is proving, K16_ERR_NO_DEVICE when the object is not
+ * ready.  Once set, FullProver::prove, k16_fullprover_prove_mem and k16_fullprover_prove_compact answer a witness whose check is
+ * BROKEN or WITNESS_REFUSED with ProverError::INVALID_INPUT / K16_ERR_FORMAT, with or without k16_fullprover_set_verify (with
+ * both on, either one rejecting is enough).
+ * k16_fullprover_last_rejection: what the CALLING THREAD's last prove through a FullProver was rejected for by the check --
+ * copied out of the slot before it went back to the pool, kept per thread.  *status = K16_CHECK_NONE when that prove was not
+ * rejected by the check (or the thread never proved); else BROKEN / WITNESS_REFUSED, *n_failed the exact count, h_failed (may be
+ * NULL) the lowest min(*n_failed, cap, K16_R1CS_REPORT_MAX) numbers.  With K16_LOG=1 the same goes out as one JSON log line. */
+int  k16_fullprover_set_r1cs(const void* fullprover, const char* r1cs_path);
+int  k16_fullprover_last_rejection(uint64_t* n_failed, uint32_t* h_failed, uint32_t cap, int* status);
+
 /* ---- set-up from a trapdoor: a valid proving key for any .r1cs, made on the GPU ----
  * WARNING: the key is DEVELOPMENT AND TEST MATERIAL.  Whoever holds the trapdoor can forge proofs.  A key whose trapdoor was
  * passed in, or drawn here and held in this process's memory, must never guard anything of value: production keys come from a

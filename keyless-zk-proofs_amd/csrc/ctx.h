@@ -318,6 +318,15 @@ int k16_random_scalar(uint8_t out[32]);
 namespace k16 { struct R1csFile; }
 // the context and the parsed circuit of an R1CS object (r1cs_check.hip)
 void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const k16::R1csFile** file);
+// The check under a proof (r1cs_check.hip; k16_prover_set_r1cs).  attach: K16_ERR_ARG (with the context's error text) unless r
+// lives on ctx and has the key's wire counts; makes the object's pinned record on first use.  fork: the check of the witness at
+// d_wtns / d_n16 enqueued on st, a stream of the prover's on which both are whole by stream order.  join: waits for it
+// and gives status (K16_CHECK_*), exact count and the lowest min(count, K16_R1CS_REPORT_MAX) numbers; K16_CHECK_NONE when
+// nothing was forked.  drain: waits and drops the result (a prove call that failed).
+int  k16_r1cs_attach(k16_r1cs* r, k16_ctx* ctx, uint32_t n_vars, uint32_t n_public);
+int  k16_r1cs_fork(k16_r1cs* r, hipStream_t st, const k16::Fr* d_wtns, const uint16_t* d_n16);
+int  k16_r1cs_join(k16_r1cs* r, int* status, uint64_t* n_failed, uint32_t* lowest);
+void k16_r1cs_drain(k16_r1cs* r);
 
 // host-side helpers implemented in ntt.hip
 int k16_ntt_get_table(k16_ctx* ctx, uint64_t max_domain, k16_ntt_table** out);

@@ -12,6 +12,10 @@
 
 #include "../../include/k16.h"
 #include <time.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 #include "../../include/k16_fullprover.hpp"
 
 namespace {
@@ -68,6 +72,15 @@ std::vector<int> device_list()
     return devs;
 }
 
+// k16_fullprover_last_rejection: what the calling thread's last prove through a FullProver was rejected for by the R1CS check
+// (copied out of the slot while the thread still holds it: the pool serves concurrent callers, a per-object "last" would race)
+struct Rejection {
+    int      status   = K16_CHECK_NONE;
+    uint64_t n_failed = 0;
+    uint32_t lowest[K16_R1CS_REPORT_MAX];
+};
+thread_local Rejection t_rejection;
+
 } // namespace
 
 class FullProverImpl
@@ -77,6 +90,7 @@ public:
         k16_ctx*    ctx    = nullptr;
         k16_prover* prover = nullptr;
         k16_vk*     vk     = nullptr; // k16_fullprover_set_verify: the slot's verification key, built from the zkey and attached to its prover
+        k16_r1cs*   r1cs   = nullptr; // k16_fullprover_set_r1cs: the slot's copy of the circuit, attached to its prover
         int         device = 0;
         bool        busy   = false;
         bool        dead   = false; // a device fault hit this slot and rebuilding it failed: never handed out again
@@ -86,6 +100,9 @@ public:
     // k16_fullprover_set_verify: every proof is checked on the GPU before it is handed out (include/k16.h, verified proving);
     // a rejected proof -- the witness does not satisfy the circuit -- is answered with INVALID_INPUT / K16_ERR_FORMAT
     bool                    verify = false;
+    // k16_fullprover_set_r1cs: every witness is checked against the circuit under its proof (include/k16.h, checked proving); one
+    // that breaks a constraint, or is refused, is answered with INVALID_INPUT / K16_ERR_FORMAT.  Empty: off
+    std::string             r1cs_path;
     std::mutex              mu;
     std::condition_variable cv;
 
@@ -97,9 +114,11 @@ public:
     {
         if (s->prover) k16_prover_destroy(s->prover);
         if (s->vk) k16_vk_destroy(s->vk);
+        if (s->r1cs) k16_r1cs_destroy(s->r1cs);
         if (s->ctx) k16_ctx_destroy(s->ctx);
         s->prover = nullptr;
         s->vk     = nullptr;
+        s->r1cs   = nullptr;
         s->ctx    = nullptr;
     }
     // verification on: the slot's key from the zkey's sections 2 and 3, attached to its prover
@@ -115,6 +134,49 @@ public:
         if (s->prover) (void)k16_prover_set_vk(s->prover, nullptr);
         if (s->vk) k16_vk_destroy(s->vk);
         s->vk = nullptr;
+    }
+    // checking on: the slot's own copy of the circuit, attached to its prover
+    int attach_r1cs(Slot* s) const
+    {
+        if (r1cs_path.empty() || s->r1cs) return K16_OK;
+        int rc = k16_r1cs_create(s->ctx, r1cs_path.c_str(), &s->r1cs);
+        if (rc == K16_OK) rc = k16_prover_set_r1cs(s->prover, s->r1cs);
+        return rc;
+    }
+    static void detach_r1cs(Slot* s)
+    {
+        if (s->prover) (void)k16_prover_set_r1cs(s->prover, nullptr);
+        if (s->r1cs) k16_r1cs_destroy(s->r1cs);
+        s->r1cs = nullptr;
+    }
+    // After a prove call on the slot, while the caller still holds it.  rc: the call's status, or REJECTED -- a proof was made
+    // and the pairing check rejects it.  The R1CS check's finding goes into the calling thread's record; a rejection by either
+    // check is answered with K16_ERR_FORMAT.  Nothing attached, a failed call: status NONE.
+    static constexpr int REJECTED = -1000;
+    int after_prove(Slot* s, int rc) const
+    {
+        const bool by_pairing = rc == REJECTED;
+        const bool by_check   = rejected_by_check(s, by_pairing ? 0 : rc);
+        return (by_pairing || (by_check && rc >= 0)) ? (int)K16_ERR_FORMAT : rc;
+    }
+    bool rejected_by_check(Slot* s, int rc) const
+    {
+        t_rejection.status   = K16_CHECK_NONE;
+        t_rejection.n_failed = 0;
+        if (rc < 0 || !s->r1cs) return false;
+        int      status = K16_CHECK_NONE;
+        uint64_t n      = 0;
+        if (k16_prover_last_check(s->prover, &status, &n, t_rejection.lowest, K16_R1CS_REPORT_MAX) != K16_OK) return false;
+        if (status != K16_CHECK_BROKEN && status != K16_CHECK_WITNESS_REFUSED) return false;
+        t_rejection.status   = status;
+        t_rejection.n_failed = n;
+        if (log_on()) {
+            std::string msg = status == K16_CHECK_BROKEN ? "witness rejected by the R1CS check: " + std::to_string(n) + " broken constraints, lowest ["
+                                                         : std::string("witness refused by the R1CS check: a value >= r, or wire 0 != 1 [");
+            for (uint64_t k = 0; k < n && k < K16_R1CS_REPORT_MAX; k++) msg += (k ? "," : "") + std::to_string(t_rejection.lowest[k]);
+            log_line("ERROR", (msg + "]").c_str());
+        }
+        return true;
     }
     // blocks until a prover is free; proofs of concurrent callers run on different slots.  nullptr: every slot is dead.
     Slot* acquire()
@@ -144,7 +206,7 @@ public:
             drop(s);
             // (from the key FILE, not from a sibling's resident copy: after a device fault nothing on that device is trusted)
             ok = k16_ctx_create(s->device, &s->ctx) == K16_OK && k16_prover_create(s->ctx, zkey_path.c_str(), &s->prover) == K16_OK &&
-                 attach_vk(s) == K16_OK;
+                 attach_vk(s) == K16_OK && attach_r1cs(s) == K16_OK;
             if (ok) {
                 int sharing = 0;
                 for (auto& o : slots) sharing += o.device == s->device;
@@ -300,9 +362,10 @@ extern "C" int k16_fullprover_prove_mem(const void* fullprover, const void* wtns
             if (fp->impl->verify) {
                 uint8_t ok = 0;
                 rc = k16_prover_prove_mem_verified(slot->prover, wtns_values, n_values, nullptr, nullptr, out_json, cap, nullptr, nullptr, &ok);
-                if (rc >= 0 && !ok) rc = K16_ERR_FORMAT; // rejected by the check: the witness does not satisfy the circuit
+                if (rc >= 0 && !ok) rc = FullProverImpl::REJECTED; // by the pairing check: the witness does not satisfy the circuit
             } else
                 rc = k16_prover_prove_mem(slot->prover, wtns_values, n_values, nullptr, nullptr, out_json, cap, nullptr);
+            rc = fp->impl->after_prove(slot, rc);
             if (rc == K16_ERR_HIP || rc == K16_ERR_NO_DEVICE) fp->impl->quarantine(slot);
         }
         if (prover_time_ms)
@@ -351,6 +414,84 @@ extern "C" int k16_fullprover_set_verify(const void* fullprover, int on)
     } catch (...) {
         return K16_ERR_HIP;
     }
+}
+
+// k16_r1cs_match_zkey over the key FILE (mapped read-only for the comparison)
+static int match_zkey_file(k16_ctx* ctx, const k16_r1cs* r, const char* zkey_path, uint32_t* mismatch)
+{
+    const int fd = open(zkey_path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return K16_ERR_IO;
+    struct stat st;
+    void*       base = MAP_FAILED;
+    if (fstat(fd, &st) == 0 && st.st_size > 0) base = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (base == MAP_FAILED) return K16_ERR_IO;
+    const int rc = k16_r1cs_match_zkey(ctx, r, base, (size_t)st.st_size, mismatch);
+    munmap(base, (size_t)st.st_size);
+    return rc;
+}
+
+// Checked proving behind the facade (include/k16.h).  All or nothing, as k16_fullprover_set_verify: the circuit is compared with
+// the zkey once, then every live slot gets a copy of its own; when one cannot, checking stays off.
+extern "C" int k16_fullprover_set_r1cs(const void* fullprover, const char* r1cs_path)
+{
+    try {
+        FullProverImpl* impl = impl_of(fullprover);
+        if (!impl) return K16_ERR_NO_DEVICE;
+        std::lock_guard<std::mutex> lk(impl->mu);
+        for (auto& s : impl->slots)
+            if (s.busy) return K16_ERR_ARG; // a proof in flight: switch before the first prove, or between waves
+        impl->r1cs_path.clear();
+        for (auto& s : impl->slots) FullProverImpl::detach_r1cs(&s);
+        if (!r1cs_path) return K16_OK;
+        impl->r1cs_path = r1cs_path;
+        int  rc      = K16_OK;
+        bool matched = false;
+        for (auto& s : impl->slots) {
+            if (s.dead) continue;
+            if ((rc = k16_r1cs_create(s.ctx, r1cs_path, &s.r1cs)) != K16_OK) {
+                fprintf(stderr, "k16 FullProver: %s: %s\n", r1cs_path, k16_last_error(s.ctx));
+                if (rc == K16_ERR_IO || rc == K16_ERR_CURVE || rc == K16_ERR_ARG) rc = K16_ERR_FORMAT; // (an unusable file, whatever the reason)
+                break;
+            }
+            if (!matched) { // once: do the circuit and the proving key belong together?
+                uint32_t mismatch = 0;
+                rc = match_zkey_file(s.ctx, s.r1cs, impl->zkey_path.c_str(), &mismatch);
+                if (rc == K16_OK && mismatch) rc = K16_ERR_FORMAT;
+                if (rc != K16_OK) {
+                    fprintf(stderr, "k16 FullProver: %s is not the circuit of %s: %s\n", r1cs_path, impl->zkey_path.c_str(),
+                            k16_last_error(s.ctx));
+                    log_line("ERROR", "R1CS check asked for but the circuit is not the proving key's");
+                    if (rc != K16_ERR_NOMEM && rc != K16_ERR_HIP) rc = K16_ERR_FORMAT;
+                    break;
+                }
+                matched = true;
+            }
+            if ((rc = k16_prover_set_r1cs(s.prover, s.r1cs)) != K16_OK) {
+                fprintf(stderr, "k16 FullProver: %s\n", k16_last_error(s.ctx));
+                break;
+            }
+        }
+        if (rc != K16_OK) {
+            impl->r1cs_path.clear();
+            for (auto& s : impl->slots) FullProverImpl::detach_r1cs(&s);
+        }
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return K16_ERR_NOMEM;
+    } catch (...) {
+        return K16_ERR_HIP;
+    }
+}
+
+extern "C" int k16_fullprover_last_rejection(uint64_t* n_failed, uint32_t* h_failed, uint32_t cap, int* status)
+{
+    if (!n_failed || !status) return K16_ERR_ARG;
+    *status   = t_rejection.status;
+    *n_failed = t_rejection.status == K16_CHECK_BROKEN ? t_rejection.n_failed : 0;
+    if (h_failed)
+        for (uint64_t k = 0; k < *n_failed && k < cap && k < K16_R1CS_REPORT_MAX; k++) h_failed[k] = t_rejection.lowest[k];
+    return K16_OK;
 }
 
 namespace {
@@ -421,9 +562,10 @@ extern "C" int k16_fullprover_prove_compact(const void* fullprover, void* lease,
         if (impl->verify) {
             uint8_t ok = 0;
             rc = k16_prover_prove_compact_verified(slot->prover, n_wide, nullptr, nullptr, out_json, cap, nullptr, nullptr, &ok);
-            if (rc >= 0 && !ok) rc = K16_ERR_FORMAT; // rejected by the check: the witness does not satisfy the circuit
+            if (rc >= 0 && !ok) rc = FullProverImpl::REJECTED; // by the pairing check: the witness does not satisfy the circuit
         } else
             rc = k16_prover_prove_compact(slot->prover, n_wide, nullptr, nullptr, out_json, cap, nullptr);
+        rc = impl->after_prove(slot, rc);
         if (rc == K16_ERR_HIP || rc == K16_ERR_NO_DEVICE) impl->quarantine(slot);
         if (prover_time_ms)
             *prover_time_ms = (int)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
@@ -468,10 +610,11 @@ ProverResponse FullProver::prove(const char* input) const
                 rc = k16_prover_prove_file_verified(slot->prover, input, nullptr, nullptr, json, sizeof json, &dev_ms, &prove_ms, nullptr, &ok);
                 if (rc >= 0 && !ok) {
                     log_line("ERROR", "proof rejected by the GPU check: the witness does not satisfy the circuit");
-                    rc = K16_ERR_FORMAT; // -> INVALID_INPUT below
+                    rc = FullProverImpl::REJECTED; // -> INVALID_INPUT below
                 }
             } else
                 rc = k16_prover_prove_file_timed(slot->prover, input, nullptr, nullptr, json, sizeof json, &dev_ms, &prove_ms);
+            rc = impl->after_prove(slot, rc); // (the R1CS check's finding; a rejection by either check -> INVALID_INPUT below)
             if (rc < 0 && rc != K16_ERR_CURVE && log_on())
                 fprintf(stderr, "k16 FullProver::prove failed: %s\n", k16_last_error(slot->ctx));
             // A HIP failure is the DEVICE's fault, not the caller's: PROVER_NOT_READY (the service's retry / failover class,

@@ -385,6 +385,11 @@ struct k16_prover {
     // d_wtns / d_n16 hold the complete witness of the last prove call: set by a prove that succeeded (plain or compact
     // upload), cleared when one starts -- a failed or aborted prove leaves them half written (k16_prover_witness_view)
     bool wtns_complete = false;
+    // k16_prover_set_r1cs: the circuit every prove call checks its witness against (not owned), and what the last call found
+    k16_r1cs* r1cs         = nullptr;
+    int       check_status = K16_CHECK_NONE;
+    uint64_t  check_failed = 0;
+    uint32_t  check_lowest[K16_R1CS_REPORT_MAX] = {0};
 };
 
 // Host side of the compact upload: the context's host threads (k16_ctx_pool) each scan a contiguous range of the witness.
@@ -897,6 +902,8 @@ extern "C" int k16_prover_create_shared(k16_ctx* ctx, const k16_prover* other, k
     p->last_h.clear();
     p->warmup_rc = 0;
     p->wtns_complete = false;
+    p->r1cs          = nullptr; // (the other prover's circuit lives on the other context)
+    p->check_status  = K16_CHECK_NONE;
     const size_t   nv = p->n_vars;
     const uint32_t N  = p->domain_size;
     K16_HIP_P(ctx, hipSetDevice(ctx->device), p);
@@ -1082,9 +1089,14 @@ static int prove_guarded(k16_prover* p, const void* h_wtns, uint64_t n_vars, int
     return k16_guard((p ? p->ctx : nullptr), [&]() -> int {
     if (!p || (!h_wtns && prepacked < 0) || !out_json) return K16_ERR_ARG;
     p->wtns_complete = false;
+    p->check_status  = K16_CHECK_NONE;
     int rc;
     try {
         rc = prove_mem_inner(p, h_wtns, n_vars, prepacked, r_in, s_in, out_json, cap, device_ms, vr);
+        if (p->r1cs && rc >= 0) { // the check that rode on this proof: joined here, long after its 0.1 ms of kernels ended
+            const int rj = k16_r1cs_join(p->r1cs, &p->check_status, &p->check_failed, p->check_lowest);
+            if (rj) rc = rj;
+        }
     } catch (const std::bad_alloc&) {
         rc = K16_ERR_NOMEM;
         try {
@@ -1106,6 +1118,8 @@ static int prove_guarded(k16_prover* p, const void* h_wtns, uint64_t n_vars, int
         }
         (void)k16_msm_abort_all(ctx); // overwrites ctx->err only when an MSM in flight failed itself
         if (p->st2) (void)hipStreamSynchronize(p->st2);
+        if (p->r1cs) k16_r1cs_drain(p->r1cs); // (the check of this call's witness: waited for, its result dropped)
+        p->check_status = K16_CHECK_NONE;
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream); // (the witness expansion: it writes the packer's bad-entry flag)
         ctx->forced_c          = 0;
         ctx->parallel_combine  = false;
@@ -1411,6 +1425,13 @@ static int prove_mem_inner(k16_prover* p, const void* h_wtns, uint64_t n_vars, i
         return rc;
     }
     ctx->cur_lane = 0;
+    // A circuit is attached: the check of THIS witness goes onto lane 1's stream BEHIND the H MSM -- the proof's last device
+    // work.  The stream waited for ev_w above, the event after which d_wtns and d_n16 are whole for all three upload forms
+    // (plain: copy + k_wtns_n16; packed and compact: the two expansion kernels; all on lane 0's stream before the record).  The
+    // MSM's finish waits for the event behind ITS download, not for the stream: the check's 0.1 ms run on the GPU the proof has
+    // left, under the host's combine, affine conversion, JSON and pairing check.  A stream of its own -- the sixth of a verified
+    // prove -- cost every proof 0.5 ms.  prove_guarded joins it on every way out.
+    if (p->r1cs && (rc = k16_r1cs_fork(p->r1cs, s1, p->d_wtns, p->d_n16))) return rc;
     // groth16.cpp:325-352 : blinding (host; six single scalar multiplications).  Everything that does not
     // need an MSM result is computed now, while the GPU is busy; the rest right after the MSM it needs.
     G1Xyzz d1     = G1Xyzz::from_aff(p->delta1);
@@ -1542,6 +1563,31 @@ extern "C" int k16_prover_set_vk(k16_prover* p, const k16_vk* vk)
         return K16_ERR_ARG;
     }
     p->vk = vk;
+    return K16_OK;
+}
+
+// ---- checked proving (include/k16.h): the R1CS check of csrc/r1cs_check.hip rides on every prove call
+extern "C" int k16_prover_set_r1cs(k16_prover* p, k16_r1cs* r)
+{
+    if (!p) return K16_ERR_ARG;
+    return k16_guard(p->ctx, [&]() -> int {
+    if (r) {
+        const int rc = k16_r1cs_attach(r, p->ctx, p->n_vars, p->n_public);
+        if (rc) return rc;
+    }
+    p->r1cs         = r;
+    p->check_status = K16_CHECK_NONE;
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_prover_last_check(const k16_prover* p, int* status, uint64_t* n_failed, uint32_t* h_failed, uint32_t cap)
+{
+    if (!p || !status || !n_failed) return K16_ERR_ARG;
+    *status   = p->check_status;
+    *n_failed = p->check_status == K16_CHECK_BROKEN ? p->check_failed : 0;
+    if (h_failed)
+        for (uint64_t k = 0; k < *n_failed && k < cap && k < K16_R1CS_REPORT_MAX; k++) h_failed[k] = p->check_lowest[k];
     return K16_OK;
 }
 

@@ -11,6 +11,9 @@
 // order, the same for every run (an atomically appended list would come in a different order each time).
 // A witness with a wire >= r, or with wire 0 != 1, is refused (K16_ERR_FORMAT) by k_r1cs_wtns, the pass that also makes the
 // n16 words of an uploaded witness: every constraint can hold for an assignment with wire 0 = 2, yet no proof of it verifies.
+// Under a proof (k16_prover_set_r1cs; ctx.h k16_r1cs_fork / _join) the same three kernels run on a stream the prover names, behind
+// the proof's witness upload, and k_r1cs_summary condenses mask and flags into one record in pinned, device-mapped memory: the
+// prove call reads 272 bytes at its join instead of copying and walking the mask.
 #include <stdio.h>
 #include <string.h>
 #include <memory>
@@ -79,6 +82,58 @@ __global__ void __launch_bounds__(256) k_r1cs_judge(const Fr* __restrict__ rows,
     if ((threadIdx.x & 63u) == 0 && (i >> 6) < n_words) mask[i >> 6] = votes;
 }
 
+// What a prove call keeps of its check (pinned, device-mapped; read by the host after the check is joined).
+struct CheckRecord {
+    unsigned long long flags;                    // WTNS_* of k_r1cs_wtns
+    unsigned long long count;                    // exact number of broken constraints
+    uint32_t           lowest[K16_R1CS_REPORT_MAX]; // the lowest min(count, K16_R1CS_REPORT_MAX) of them, ascending
+};
+
+// mask[n_words] | flags -> rec.  ONE workgroup of 256 lanes walks the mask in tiles of 256 words (16384 constraints), a word per
+// lane: popcount, an ordered scan over the tile (shuffles inside a wave, the four wave totals through LDS) on top of the
+// running total of the tiles before gives every word the rank of its first set bit; a word whose rank is below
+// K16_R1CS_REPORT_MAX writes its bits' numbers at rank, rank + 1, ... -- every slot of the list has exactly one writer,
+// whatever the order the lanes run in.  The tile of the next round is loaded before this round's scan.
+__global__ void __launch_bounds__(256) k_r1cs_summary(const unsigned long long* __restrict__ mask, uint32_t n_words,
+                                                      CheckRecord* __restrict__ rec)
+{
+    __shared__ uint32_t wave_total[2][4]; // (two sets, by the tile's parity: one barrier a tile)
+    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long  running = 0; // broken constraints in the tiles before this one (the same in every lane)
+    unsigned long long  next    = threadIdx.x < n_words ? mask[threadIdx.x] : 0ull;
+    for (uint32_t base = 0; base < n_words; base += 256u) {
+        const uint32_t           w = base + threadIdx.x;
+        const unsigned long long m = next;
+        next                       = w + 256u < n_words ? mask[w + 256u] : 0ull; // (n_words <= 2^26: no wrap)
+        const uint32_t mine = (uint32_t)__popcll(m);
+        uint32_t       incl = mine; // inclusive scan over the wave
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        uint32_t* totals = wave_total[(base >> 8) & 1u];
+        if (lane == 63u) totals[wave] = incl;
+        __syncthreads(); // (a wave writes this set again two tiles on: every wave has passed the next tile's barrier by then)
+        uint32_t before = 0, tile = 0;
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t t = totals[k];
+            if (k < wave) before += t;
+            tile += t;
+        }
+        unsigned long long rank = running + before + (incl - mine);
+        unsigned long long bits = m;
+        while (bits && rank < (unsigned long long)K16_R1CS_REPORT_MAX) {
+            rec->lowest[rank++] = w * 64u + (uint32_t)__ffsll((long long)bits) - 1u;
+            bits &= bits - 1;
+        }
+        running += tile;
+    }
+    if (threadIdx.x == 0) {
+        rec->flags = mask[n_words];
+        rec->count = running;
+    }
+}
+
 } // namespace
 
 struct k16_r1cs {
@@ -98,6 +153,9 @@ struct k16_r1cs {
     unsigned long long* d_mask = nullptr; // [n_words] verdicts | [1] witness flags
     unsigned long long* h_mask = nullptr; // pinned copy
     bool                have_values = false; // d_rows holds the sums of a completed check (k16_r1cs_last_values)
+    // attached to a prover (k16_r1cs_attach): made by the first attach, kept until the object goes
+    CheckRecord *h_rec = nullptr, *d_rec = nullptr; // pinned, device-mapped
+    hipStream_t  forked_on = nullptr; // the prover's stream a check is (or may be) in flight on; null: none
 };
 
 void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const R1csFile** file)
@@ -114,6 +172,8 @@ static void r1cs_free(k16_r1cs* r)
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (r->h_mask) (void)hipHostFree(r->h_mask);
+    if (r->forked_on) (void)hipStreamSynchronize(r->forked_on);
+    if (r->h_rec) (void)hipHostFree(r->h_rec);
     delete r;
 }
 
@@ -213,11 +273,10 @@ extern "C" int k16_r1cs_info(const k16_r1cs* r, uint32_t* n_wires, uint32_t* n_p
     return K16_OK;
 }
 
-// The check proper, on the context's stream: d_wtns holds n_wires values; d_n16 their 16-bit words, or null when this call
-// is to make them (into r->d_n16).  Whatever fails, the stream is drained before the call returns.
-static int r1cs_enqueue(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint16_t* d_n16)
+// The three kernels of a check on st: d_wtns holds n_wires values; d_n16 their 16-bit words, or null when this call is to make
+// them (into r->d_n16).
+static int r1cs_launch(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint16_t* d_n16, hipStream_t st)
 {
-    hipStream_t st = ctx->stream;
     K16_HIP(ctx, hipMemsetAsync(r->d_mask + r->n_words, 0, 8, st));
     hipLaunchKernelGGL(k_r1cs_wtns, dim3((r->n_wires + 255) / 256), dim3(256), 0, st, (const uint4*)d_wtns, r->n_wires,
                        d_n16 ? nullptr : r->d_n16, r->d_mask + r->n_words);
@@ -234,8 +293,77 @@ static int r1cs_enqueue(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint1
         }
     }
     K16_HIP(ctx, hipGetLastError());
+    return K16_OK;
+}
+
+// The check proper, on the context's stream.  Whatever fails, the stream is drained before the caller returns.
+static int r1cs_enqueue(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint16_t* d_n16)
+{
+    hipStream_t st = ctx->stream;
+    const int   rc = r1cs_launch(ctx, r, d_wtns, d_n16, st);
+    if (rc) return rc;
     K16_HIP(ctx, hipMemcpyAsync(r->h_mask, r->d_mask, ((size_t)r->n_words + 1) * 8, hipMemcpyDeviceToHost, st));
     K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+// ---- the check under a proof (ctx.h; prover.hip k16_prover_set_r1cs)
+int k16_r1cs_attach(k16_r1cs* r, k16_ctx* ctx, uint32_t n_vars, uint32_t n_public)
+{
+    if (r->ctx != ctx || r->n_wires != n_vars || r->n_public != n_public) {
+        ctx->err = r->ctx != ctx            ? "k16_prover_set_r1cs: the R1CS object belongs to another context"
+                   : r->n_wires != n_vars ? "k16_prover_set_r1cs: the circuit's wire count is not the proving key's nVars"
+                                          : "k16_prover_set_r1cs: the circuit's public wire count is not the proving key's nPublic";
+        return K16_ERR_ARG;
+    }
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    if (!r->h_rec) {
+        K16_HIP(ctx, hipHostMalloc((void**)&r->h_rec, sizeof(CheckRecord), hipHostMallocMapped | hipHostMallocCoherent));
+        K16_HIP(ctx, hipHostGetDevicePointer((void**)&r->d_rec, r->h_rec, 0));
+    }
+    return K16_OK;
+}
+
+int k16_r1cs_fork(k16_r1cs* r, hipStream_t st, const Fr* d_wtns, const uint16_t* d_n16)
+{
+    k16_ctx* ctx   = r->ctx;
+    r->have_values = false;
+    r->forked_on   = st;
+    const int rc   = r1cs_launch(ctx, r, d_wtns, d_n16, st);
+    if (rc) return rc;
+    {
+        k16_stat_scope sc(ctx, "r1cs_summary", st);
+        hipLaunchKernelGGL(k_r1cs_summary, dim3(1), dim3(256), 0, st, r->d_mask, r->n_words, r->d_rec);
+    }
+    K16_HIP(ctx, hipGetLastError());
+    return K16_OK;
+}
+
+void k16_r1cs_drain(k16_r1cs* r)
+{
+    if (r->forked_on) (void)hipStreamSynchronize(r->forked_on);
+    r->forked_on = nullptr;
+}
+
+int k16_r1cs_join(k16_r1cs* r, int* status, uint64_t* n_failed, uint32_t* lowest)
+{
+    k16_ctx* ctx = r->ctx;
+    *status      = K16_CHECK_NONE;
+    *n_failed    = 0;
+    if (!r->forked_on) return K16_OK;
+    hipStream_t st = r->forked_on;
+    r->forked_on   = nullptr;
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    const CheckRecord* rec = r->h_rec;
+    if (rec->flags) {
+        *status = K16_CHECK_WITNESS_REFUSED;
+        return K16_OK;
+    }
+    r->have_values = true;
+    *n_failed      = rec->count;
+    *status        = rec->count ? K16_CHECK_BROKEN : K16_CHECK_SATISFIED;
+    const uint64_t n = std::min<uint64_t>(rec->count, K16_R1CS_REPORT_MAX);
+    for (uint64_t k = 0; k < n; k++) lowest[k] = rec->lowest[k];
     return K16_OK;
 }
 

@@ -48,6 +48,7 @@ SYMBOLS = [
     "k16_prover_prove_compact_verified", "k16_prover_prove_file_verified", "k16_verify_split_gt", "k16_fullprover_set_verify",
     "k16_r1cs_create", "k16_r1cs_create_mem", "k16_r1cs_destroy", "k16_r1cs_info", "k16_r1cs_check_mem", "k16_r1cs_check_file",
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
+    "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
     "k16_msm_sharded_last_error", "k16_msm_sharded_set_bases", "k16_msm_sharded_set_bases_device", "k16_msm_sharded_run",
@@ -172,6 +173,10 @@ def load():
     L.k16_r1cs_check_prover_witness.argtypes = [vp, vp, C.POINTER(u64), vp, u32]
     L.k16_r1cs_last_values.argtypes = [vp, u32, vp]
     L.k16_r1cs_match_zkey.argtypes = [vp, vp, vp, sz, C.POINTER(u32)]
+    L.k16_prover_set_r1cs.argtypes = [vp, vp]
+    L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
+    L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
+    L.k16_fullprover_last_rejection.argtypes = [C.POINTER(u64), vp, u32, C.POINTER(i32)]
     L.k16_r1cs_setup_size.argtypes = [vp, C.POINTER(u64)]
     L.k16_r1cs_setup.argtypes = [vp, vp, vp, vp, sz, C.POINTER(sz)]
     L.k16_r1cs_setup_file.argtypes = [vp, vp, vp, C.c_char_p]
@@ -516,6 +521,28 @@ def points_sum(group, parts):
     return x.tobytes(), a.tobytes()
 
 
+# k16_prover_last_check / k16_fullprover_last_rejection (include/k16.h)
+R1CS_REPORT_MAX = 64
+CHECK_NONE, CHECK_SATISFIED, CHECK_BROKEN, CHECK_WITNESS_REFUSED = 0, 1, 2, 3
+
+
+def fullprover_set_r1cs(fullprover, r1cs_path):
+    """k16_fullprover_set_r1cs on a FullProver object's address (int or c_void_p); r1cs_path None detaches.  Returns the status."""
+    return int(load().k16_fullprover_set_r1cs(fullprover, str(r1cs_path).encode() if r1cs_path is not None else None))
+
+
+def fullprover_last_rejection(cap=R1CS_REPORT_MAX):
+    """k16_fullprover_last_rejection: (status, n_failed, lowest constraint numbers) of the calling thread's last prove through a
+    FullProver; CHECK_NONE when the R1CS check did not reject it."""
+    cap = int(cap)
+    out = np.zeros(max(cap, 1), dtype=np.uint32)
+    st, n = C.c_int32(), C.c_uint64()
+    rc = load().k16_fullprover_last_rejection(C.byref(n), _p(out), cap, C.byref(st))
+    if rc:
+        raise K16Error(rc)
+    return int(st.value), int(n.value), out[:min(int(n.value), cap, R1CS_REPORT_MAX)].tolist()
+
+
 class Prover:
     """Mirror of the reference's FullProver(zkey).prove(wtns) (fullprover.hpp:52-64) over the C ABI."""
 
@@ -616,6 +643,29 @@ class Prover:
         """k16_prover_prove_compact_verified: as prove_mem_verified, for the witness compact_buffers() holds."""
         L, h = self.ctx.L, self.h
         return self._verified(lambda *a: L.k16_prover_prove_compact_verified(h, int(n_wide), *a), r, s)
+
+    def prove_file_verified(self, wtns_path, r=None, s=None):
+        """k16_prover_prove_file_verified: as prove_mem_verified, for a .wtns file."""
+        L, h, wall = self.ctx.L, self.h, C.c_float()
+        path = str(wtns_path).encode()
+        return self._verified(lambda R_, S_, buf, cap, ms, proof, ok: L.k16_prover_prove_file_verified(
+            h, path, R_, S_, buf, cap, ms, C.byref(wall), proof, ok), r, s)
+
+    def set_r1cs(self, r1cs):
+        """k16_prover_set_r1cs: the R1cs every prove call from now on checks its witness against (None detaches).  The prover
+        does not own it: keep it alive while it is attached."""
+        rc = self.ctx.L.k16_prover_set_r1cs(self.h, r1cs.h if r1cs is not None else None)
+        if rc < 0:
+            raise K16Error(rc, (self.ctx.L.k16_last_error(self.ctx.h) or b"").decode())
+
+    def last_check(self, cap=R1CS_REPORT_MAX):
+        """k16_prover_last_check: (status, n_failed, list of the lowest min(n_failed, cap, R1CS_REPORT_MAX) broken constraints)
+        of the last prove call; status is one of the CHECK_* values."""
+        cap = int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        st, n = C.c_int32(), C.c_uint64()
+        self.ctx._chk(self.ctx.L.k16_prover_last_check(self.h, C.byref(st), C.byref(n), _p(out), cap))
+        return int(st.value), int(n.value), out[:min(int(n.value), cap, R1CS_REPORT_MAX)].tolist()
 
     def warmup_status(self):
         return int(self.ctx.L.k16_prover_warmup_status(self.h))
