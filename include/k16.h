@@ -574,6 +574,42 @@ int  k16_r1cs_last_values(k16_r1cs* r, uint32_t constraint, void* h_out96);
  * 4 public rows -- with its constraint and wire in k16_last_error.  K16_ERR_FORMAT / K16_ERR_CURVE for an unreadable zkey. */
 int  k16_r1cs_match_zkey(k16_ctx* ctx, const k16_r1cs* r, const void* zkey, size_t size, uint32_t* mismatch);
 
+/* ---- unbound-wire scan: WHICH wires does the circuit leave free under this witness? ----
+ * The dual of the check: not "does w satisfy the circuit" but "does the circuit pin w".  With a_c, b_c, c_c the sums A.w, B.w, C.w
+ * of constraint c as the LAST completed check left them on the device, and A^, B^, C^ the MERGED coefficients of wire i in
+ * constraint c (a wire listed twice adds, as in the check), changing wire i alone by d moves the residual a_c b_c - c_c by
+ * d lin + d^2 quad,  lin = A^ b_c + B^ a_c - C^,  quad = A^ B^  (mod r).  Every wire 1 .. nWires - 1 gets a class:
+ *   K16_WIRE_BOUND    some constraint has lin != 0 or quad != 0
+ *   K16_WIRE_ABSENT   A^ = B^ = C^ = 0 in every constraint: the wire is in no term, or its coefficients cancel.  Structural, the
+ *                     same for every witness
+ *   K16_WIRE_UNBOUND  some merged coefficient is non-zero, yet lin = 0 and quad = 0 everywhere: under THIS witness every value
+ *                     of the wire leaves every residual as it is
+ * Wire 0 is the constant 1: reported BOUND, never listed.  Zero is zero modulo r (canonical form, as in the check); the scan is
+ * exact and deterministic.  It is defined for any witness a check completed on, and meant for a satisfying one.  It judges
+ * nothing: a mux input behind a zero selector is UNBOUND and legitimate.
+ *   k16_r1cs_unbound_wires     one launch over the circuit's incidences (csrc/r1cs_check.hip) on the sums of the last completed
+ *                              check: K16_ERR_ARG when none has completed on r (a refused witness completes none), exactly as
+ *                              k16_r1cs_last_values.  *n_absent / *n_unbound: how many wires of each class.  h_wires / h_class
+ *                              (either may be NULL): the lowest min(*n_absent + *n_unbound, cap) wires that are not BOUND,
+ *                              ascending, with their class -- the same list on every run.  Public wires are 1 .. nPublic, so they
+ *                              come FIRST: an unbound public wire is the finding to look at first.  h_status (may be NULL):
+ *                              n_wires bytes, the class of every wire.
+ *   k16_r1cs_wire_constraints  the constraints `wire` appears in with a non-zero merged coefficient: *n = how many, h_constraints
+ *                              (may be NULL) the lowest min(*n, cap), ascending.  Host only; needs no check.  K16_ERR_ARG for a
+ *                              wire >= nWires.
+ *   k16_r1cs_incidences        the number of (wire, constraint) pairs with a non-zero merged coefficient: what the scan walks
+ *                              (all but the column of wire 0, which is no variable).  Host only.
+ * The incidence list is built by the first of these calls and its device copy by the first scan; both stay with the object.  A
+ * circuit that is never scanned pays nothing.  K16_ERR_ARG for 2^32 incidences or more; K16_ERR_NOMEM / K16_ERR_HIP as elsewhere.
+ * THREADING: as k16_r1cs_check_*: one call at a time per object, on the context's stream.  On an object attached to a prover
+ * the scan is legal BETWEEN prove calls (the sums are the last prove's), not while one runs.  Every error leaves nothing in
+ * flight. */
+enum { K16_WIRE_BOUND = 0, K16_WIRE_ABSENT = 1, K16_WIRE_UNBOUND = 2 };
+int  k16_r1cs_unbound_wires(k16_r1cs* r, uint64_t* n_absent, uint64_t* n_unbound, uint32_t* h_wires, uint8_t* h_class, uint32_t cap,
+                            uint8_t* h_status);
+int  k16_r1cs_wire_constraints(k16_r1cs* r, uint32_t wire, uint64_t* n, uint32_t* h_constraints, uint32_t cap);
+int  k16_r1cs_incidences(k16_r1cs* r, uint64_t* n_pairs);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

@@ -14,6 +14,11 @@
 // Under a proof (k16_prover_set_r1cs; ctx.h k16_r1cs_fork / _join) the same three kernels run on a stream the prover names, behind
 // the proof's witness upload, and k_r1cs_summary condenses mask and flags into one record in pinned, device-mapped memory: the
 // prove call reads 272 bytes at its join instead of copying and walking the mask.
+// The unbound-wire scan (k16_r1cs_unbound_wires; r1cs_pairs.h) asks the dual question of the sums a
+// completed check left in d_rows: which wires could take any value without moving a residual?
+//   k_r1cs_incidences  one lane per (wire, constraint) incidence: is d(a b - c) / d(wire) or the wire's quadratic part non-zero?
+//                      A wave ORs the bits of the wires it found bound into a mask of ceil(nWires / 64) words; the host reads it.
+// Its list and its buffers are made by the first scan of an object: a circuit that is never scanned pays nothing.
 #include <stdio.h>
 #include <string.h>
 #include <memory>
@@ -21,10 +26,12 @@
 #include <vector>
 #include "ctx.h"
 #include "r1cs_file.h"
+#include "r1cs_pairs.h"
 #include "spmv_dev.h"
 
 using namespace k16;
 
+static_assert(sizeof(R1csPair) == sizeof(uint4), "an incidence is one 16-byte load");
 static_assert(R1CS_ERR_ARG == K16_ERR_ARG && R1CS_ERR_FORMAT == K16_ERR_FORMAT && R1CS_ERR_CURVE == K16_ERR_CURVE && R1CS_OK == K16_OK,
               "r1cs_file.h returns the library's status codes");
 
@@ -80,6 +87,69 @@ __global__ void __launch_bounds__(256) k_r1cs_judge(const Fr* __restrict__ rows,
     }
     const unsigned long long votes = __ballot(fail);
     if ((threadIdx.x & 63u) == 0 && (i >> 6) < n_words) mask[i >> 6] = votes;
+}
+
+// The unbound-wire scan.  Change wire i alone by d: the residual a_c b_c - c_c of constraint c moves by d lin + d^2 quad with
+//   lin = A^ b_c + B^ a_c - C^,  quad = A^ B^      (A^, B^, C^: the merged coefficients of wire i in constraint c)
+// and the wire is bound by c when lin != 0 or quad != 0 (mod r).
+// quad: r is prime, so a product of two non-zero residues is non-zero, and r1cs_pairs.h names a coefficient only when its merged
+// sum is non-zero: quad != 0 exactly when the incidence names both A^ and B^.  No product is formed for it.
+// lin, where quad = 0: at most ONE of A^, B^ is there, so lin is one product (or none) minus C^.  Scalings: a coefficient k is
+// stored as k * 2^522 mod r (coef, and side in the same scaling), a sum s lies in rows as the R' value s * 2^261; frmul9 divides
+// by 2^261:   frmul9(A^ 2^522, b 2^261) = A^ b 2^522,  frmul9(B^ 2^522, a 2^261) = B^ a 2^522,  and C^ is stored as C^ 2^522
+// -- the product and the bare C^ term carry the SAME factor 2^522, so their difference is lin * 2^522.  fr9_to_standard divides
+// by 2^261 once more and returns the canonical representative of lin * 2^261: zero exactly when r divides lin (the operands are
+// lazy representatives below 2r, as in k_r1cs_judge: only the canonical form tells r from 0).  Bounds: coefficients < r, sums
+// < 2r (+ 2^-17 r): the product is < 2r, frsub9 takes a subtrahend < 2r.
+// inc / wire: n_pairs incidences ordered by wire (the host leaves wire 0's out, see below).  Positions: < n_entries -> coef,
+// n_entries + k -> side[k], R1CS_PAIR_NONE -> 0.
+// bound: ceil(n_wires / 64) words, cleared before the launch, bit i = wire i is bound.  The list is ordered by wire, so the
+// lanes of a wave whose wires share a mask word are neighbours: their bits are ORed over the wave first and ONE lane per word
+// issues the atomicOr, and only where the word does not show the bits yet (atomics on ONE address queue up behind each other
+// across the whole device: a wire that sits in a large part of the constraints would cost one per wave); an OR gives the same
+// mask whatever order the lanes run in.  Wire 0, the constant, is BOUND by definition: the host leaves its column -- the
+// longest of a real circuit -- out of the launch.  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_incidences(const uint4* __restrict__ inc, const uint32_t* __restrict__ wire,
+                                                         uint32_t n_pairs, const Fr* __restrict__ coef, uint32_t n_entries,
+                                                         const Fr* __restrict__ side, const Fr* __restrict__ rows, uint32_t M,
+                                                         unsigned long long* bound)
+{
+    const uint32_t i    = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t       w    = 0xffffffffu; // (no wire: the lanes behind the list)
+    bool           hit  = false;
+    if (i < n_pairs) {
+        const uint4 e = inc[i]; // x: constraint, y / z / w: positions of A^ / B^ / C^
+        w             = wire[i];
+        auto at       = [&](uint32_t p) { return ld_r9(p < n_entries ? &coef[p] : &side[p - n_entries]); };
+        if (e.y != R1CS_PAIR_NONE && e.z != R1CS_PAIR_NONE) {
+            hit = true;
+        } else {
+            Fr9 lin = fq9_zero();
+            if (e.y != R1CS_PAIR_NONE) lin = frmul9(at(e.y), ld_r9(&rows[(size_t)M + e.x]));
+            if (e.z != R1CS_PAIR_NONE) lin = frmul9(at(e.z), ld_r9(&rows[e.x]));
+            if (e.w != R1CS_PAIR_NONE) lin = frsub9(lin, at(e.w));
+            const Fr d = fr9_to_standard(lin);
+            hit        = (d.v[0] | d.v[1] | d.v[2] | d.v[3] | d.v[4] | d.v[5] | d.v[6] | d.v[7]) != 0;
+        }
+    }
+    // OR of the hits of each run of lanes that share a mask word (a segmented inclusive scan upwards); its last lane stores
+    const uint32_t           word  = w >> 6;
+    const uint32_t           prev  = __shfl_up(word, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || word != prev); // first lane of each run (bit 0 is set)
+    const unsigned long long upto  = lane == 63u ? ~0ull : (1ull << (lane + 1)) - 1;     // lanes 0 .. lane
+    const uint32_t           first = 63u - (uint32_t)__clzll((long long)(heads & upto)); // my run's first lane
+    unsigned long long       bits  = hit ? 1ull << (w & 63u) : 0ull;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const unsigned long long up = __shfl_up(bits, d, 64);
+        if (lane >= first + d) bits |= up;
+    }
+    const bool last = lane == 63u || ((heads >> (lane + 1)) & 1ull) != 0;
+    // (the mask was cleared before the launch and bits are only ever set: a read that lags behind can only miss bits that are
+    // set by now -- the atomic is then issued for nothing, the mask is the same.  Other lanes update the word atomically, so
+    // the read is a relaxed atomic load and `bound` is no __restrict__ pointer: the compiler may not hoist or merge it)
+    if (last && bits && (__atomic_load_n(&bound[word], __ATOMIC_RELAXED) & bits) != bits) atomicOr(&bound[word], bits);
 }
 
 // What a prove call keeps of its check (pinned, device-mapped; read by the host after the check is joined).
@@ -146,6 +216,7 @@ struct k16_r1cs {
     uint32_t * d_rowof = nullptr, *d_wire = nullptr;
     Fr*        d_coef  = nullptr; // coefficient * 2^522 mod r, as the prover stores its own
     uint32_t   n_slices = 0, n_long = 0;
+    uint64_t   n_entries = 0; // of the plan d_coef was laid out by (r1cs_pairs.h names coefficients by position in it)
     // per check
     Fr*                 d_wtns = nullptr; // an uploaded witness (k16_r1cs_check_mem / _file)
     uint16_t*           d_n16  = nullptr;
@@ -156,6 +227,13 @@ struct k16_r1cs {
     // attached to a prover (k16_r1cs_attach): made by the first attach, kept until the object goes
     CheckRecord *h_rec = nullptr, *d_rec = nullptr; // pinned, device-mapped
     hipStream_t  forked_on = nullptr; // the prover's stream a check is (or may be) in flight on; null: none
+    // the unbound-wire scan: the list by the first call that needs it, the device side by the first scan; kept until the object goes
+    std::unique_ptr<R1csPairs> pairs;
+    uint4*                     d_inc     = nullptr; // R1csPair of every incidence of the wires 1 .. n_wires - 1
+    uint32_t*                  d_incwire = nullptr; // their wires
+    Fr*                        d_side    = nullptr; // merged sums * 2^522 mod r
+    unsigned long long *       d_bound = nullptr, *h_bound = nullptr; // [ceil(n_wires / 64)], device / pinned
+    bool                       scan_ready = false;
 };
 
 void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const R1csFile** file)
@@ -164,10 +242,22 @@ void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const R1csFile** file)
     *file = &r->file;
 }
 
+// the scan's device side (the host list stays)
+static void r1cs_scan_free(k16_r1cs* r)
+{
+    void* bufs[] = {r->d_inc, r->d_incwire, r->d_side, r->d_bound};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (r->h_bound) (void)hipHostFree(r->h_bound);
+    r->d_inc = nullptr, r->d_incwire = nullptr, r->d_side = nullptr, r->d_bound = nullptr, r->h_bound = nullptr;
+    r->scan_ready = false;
+}
+
 static void r1cs_free(k16_r1cs* r)
 {
     if (!r) return;
     if (r->ctx) (void)hipSetDevice(r->ctx->device);
+    r1cs_scan_free(r);
     void* bufs[] = {r->d_slices, r->d_longs, r->d_rowof, r->d_wire, r->d_coef, r->d_wtns, r->d_n16, r->d_rows, r->d_mask};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -212,6 +302,7 @@ extern "C" int k16_r1cs_create_mem(k16_ctx* ctx, const void* r1cs, size_t size, 
     r->n_words  = (uint32_t)(((uint64_t)r->M + 63) / 64);
     r->n_slices = plan.plan.n_slices;
     r->n_long   = plan.plan.n_long;
+    r->n_entries = plan.plan.n_entries;
     const uint64_t        n_entries = std::max<uint64_t>(plan.plan.n_entries, 1);
     std::vector<uint32_t> wire(n_entries, 0);
     std::vector<R1csFr>   vals(n_entries, R1csFr{{0, 0, 0, 0}}); // padding: coefficient 0 (times wire 0)
@@ -476,6 +567,160 @@ extern "C" int k16_r1cs_last_values(k16_r1cs* r, uint32_t constraint, void* h_ou
         const Fr v = fr9_to_standard(fr9_load(packed[m].v)); // the same host code the device runs
         memcpy((uint8_t*)h_out96 + 32 * m, v.v, 32);
     }
+    return K16_OK;
+    });
+}
+
+// ---- the unbound-wire scan
+// The incidence list, made once.  K16_ERR_ARG: 2^32 incidences or more.
+static int r1cs_pairs_get(k16_ctx* ctx, k16_r1cs* r)
+{
+    if (r->pairs) return K16_OK;
+    R1csPlan plan; // the layout k16_r1cs_create_mem uploaded: r1cs_plan_build is a function of the file alone
+    if (r1cs_plan_build(r->file, &plan)) {
+        ctx->err = "r1cs: too many terms for 32-bit entry offsets";
+        return K16_ERR_ARG;
+    }
+    if (plan.plan.n_entries != r->n_entries) { // positions would point into another layout than d_coef's
+        ctx->err = "r1cs: the rebuilt plan is not the one the coefficients were uploaded by";
+        return K16_ERR_ARG;
+    }
+    std::unique_ptr<R1csPairs> p(new R1csPairs());
+    if (r1cs_pairs_build(r->file, plan, p.get())) {
+        ctx->err = "r1cs: 2^32 (wire, constraint) incidences or more";
+        return K16_ERR_ARG;
+    }
+    r->pairs = std::move(p);
+    return K16_OK;
+}
+
+// hipMalloc for the scan: out of device memory is K16_ERR_NOMEM
+static int r1cs_scan_alloc(k16_ctx* ctx, void** p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 32));
+    if (e == hipSuccess) return K16_OK;
+    *p       = nullptr;
+    ctx->err = std::string("unbound-wire scan: hipMalloc: ") + hipGetErrorString(e);
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? K16_ERR_NOMEM : K16_ERR_HIP;
+}
+
+// list, side table and mask on the device, by the first scan
+static int r1cs_scan_upload(k16_ctx* ctx, k16_r1cs* r)
+{
+    const R1csPairs&    P    = *r->pairs;
+    const size_t        skip = P.start[1]; // wire 0's column stays on the host: see k_r1cs_incidences
+    const size_t        n = P.pair.size() - skip, words = P.present.size();
+    std::vector<R1csFr> side(P.side.size());
+    const R1csScale     to_r9(522);
+    for (size_t k = 0; k < side.size(); k++) side[k] = to_r9(P.side[k]);
+    int rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_inc, n * sizeof(R1csPair)))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_incwire, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_side, side.size() * 32))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_bound, words * 8))) return rc;
+    K16_HIP(ctx, hipHostMalloc((void**)&r->h_bound, std::max<size_t>(words * 8, 8), hipHostMallocDefault));
+    hipStream_t st = ctx->stream;
+    if (n) {
+        K16_HIP(ctx, hipMemcpyAsync(r->d_inc, P.pair.data() + skip, n * sizeof(R1csPair), hipMemcpyHostToDevice, st));
+        K16_HIP(ctx, hipMemcpyAsync(r->d_incwire, P.wire.data() + skip, n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (!side.empty()) K16_HIP(ctx, hipMemcpyAsync(r->d_side, side.data(), side.size() * 32, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipStreamSynchronize(st)); // (side is a local)
+    r->scan_ready = true;
+    return K16_OK;
+}
+
+static int r1cs_scan_run(k16_ctx* ctx, k16_r1cs* r)
+{
+    const R1csPairs& P     = *r->pairs;
+    const uint32_t   n     = (uint32_t)P.pair.size() - P.start[1]; // all but wire 0's column
+    const size_t     words = P.present.size();
+    hipStream_t      st    = ctx->stream;
+    K16_HIP(ctx, hipMemsetAsync(r->d_bound, 0, words * 8, st));
+    if (n) {
+        k16_stat_scope sc(ctx, "r1cs_incidences", st);
+        hipLaunchKernelGGL(k_r1cs_incidences, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, st, r->d_inc, r->d_incwire, n,
+                           r->d_coef, P.n_entries, r->d_side, r->d_rows, r->M, r->d_bound);
+    }
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(r->h_bound, r->d_bound, words * 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_unbound_wires(k16_r1cs* r, uint64_t* n_absent, uint64_t* n_unbound, uint32_t* h_wires, uint8_t* h_class,
+                                      uint32_t cap, uint8_t* h_status)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_absent || !n_unbound) return K16_ERR_ARG;
+    *n_absent = *n_unbound = 0;
+    k16_ctx* ctx = r->ctx;
+    if (!r->have_values || r->forked_on) {
+        ctx->err = "no completed check to scan";
+        return K16_ERR_ARG;
+    }
+    int rc = r1cs_pairs_get(ctx, r);
+    if (rc) return rc;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    if (!r->scan_ready) rc = r1cs_scan_upload(ctx, r);
+    if (!rc) rc = r1cs_scan_run(ctx, r);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream); // nothing of the scan stays in flight
+        if (!r->scan_ready) r1cs_scan_free(r);
+        return rc;
+    }
+    const R1csPairs& P = *r->pairs;
+    uint64_t         absent = 0, unbound = 0, listed = 0;
+    for (size_t w = 0; w < P.present.size(); w++) {
+        const uint32_t     in_word = (uint32_t)std::min<uint64_t>(64, (uint64_t)r->n_wires - 64 * (uint64_t)w);
+        unsigned long long valid   = in_word == 64 ? ~0ull : (1ull << in_word) - 1;
+        if (w == 0) valid &= ~1ull; // wire 0 is the constant
+        const unsigned long long free_ = ~r->h_bound[w] & valid, here = P.present[w];
+        absent += (uint64_t)__builtin_popcountll(free_ & ~here);
+        unbound += (uint64_t)__builtin_popcountll(free_ & here);
+        if (h_status)
+            for (uint32_t b = 0; b < in_word; b++)
+                h_status[64 * w + b] = (free_ >> b) & 1 ? ((here >> b) & 1 ? K16_WIRE_UNBOUND : K16_WIRE_ABSENT) : K16_WIRE_BOUND;
+        for (unsigned long long m = free_; m && listed < cap && (h_wires || h_class); m &= m - 1, listed++) {
+            const uint32_t b = (uint32_t)__builtin_ctzll(m);
+            if (h_wires) h_wires[listed] = (uint32_t)(64 * w + b);
+            if (h_class) h_class[listed] = (here >> b) & 1 ? K16_WIRE_UNBOUND : K16_WIRE_ABSENT;
+        }
+    }
+    *n_absent  = absent;
+    *n_unbound = unbound;
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_r1cs_wire_constraints(k16_r1cs* r, uint32_t wire, uint64_t* n, uint32_t* h_constraints, uint32_t cap)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n) return K16_ERR_ARG;
+    *n = 0;
+    if (wire >= r->n_wires) {
+        r->ctx->err = "wire number out of range";
+        return K16_ERR_ARG;
+    }
+    const int rc = r1cs_pairs_get(r->ctx, r);
+    if (rc) return rc;
+    const R1csPairs& P = *r->pairs;
+    *n                 = P.start[wire + 1] - P.start[wire];
+    const uint64_t k_n = std::min<uint64_t>(*n, cap);
+    for (uint64_t k = 0; h_constraints && k < k_n; k++) h_constraints[k] = P.pair[P.start[wire] + k].constraint;
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_r1cs_incidences(k16_r1cs* r, uint64_t* n_pairs)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_pairs) return K16_ERR_ARG;
+    *n_pairs     = 0;
+    const int rc = r1cs_pairs_get(r->ctx, r);
+    if (rc) return rc;
+    *n_pairs = r->pairs->n_pairs();
     return K16_OK;
     });
 }

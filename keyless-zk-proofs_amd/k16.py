@@ -48,6 +48,7 @@ SYMBOLS = [
     "k16_prover_prove_compact_verified", "k16_prover_prove_file_verified", "k16_verify_split_gt", "k16_fullprover_set_verify",
     "k16_r1cs_create", "k16_r1cs_create_mem", "k16_r1cs_destroy", "k16_r1cs_info", "k16_r1cs_check_mem", "k16_r1cs_check_file",
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
+    "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences",
     "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
@@ -173,6 +174,9 @@ def load():
     L.k16_r1cs_check_prover_witness.argtypes = [vp, vp, C.POINTER(u64), vp, u32]
     L.k16_r1cs_last_values.argtypes = [vp, u32, vp]
     L.k16_r1cs_match_zkey.argtypes = [vp, vp, vp, sz, C.POINTER(u32)]
+    L.k16_r1cs_unbound_wires.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), vp, vp, u32, vp]
+    L.k16_r1cs_wire_constraints.argtypes = [vp, u32, C.POINTER(u64), vp, u32]
+    L.k16_r1cs_incidences.argtypes = [vp, C.POINTER(u64)]
     L.k16_prover_set_r1cs.argtypes = [vp, vp]
     L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
     L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
@@ -524,6 +528,7 @@ def points_sum(group, parts):
 # k16_prover_last_check / k16_fullprover_last_rejection (include/k16.h)
 R1CS_REPORT_MAX = 64
 CHECK_NONE, CHECK_SATISFIED, CHECK_BROKEN, CHECK_WITNESS_REFUSED = 0, 1, 2, 3
+WIRE_BOUND, WIRE_ABSENT, WIRE_UNBOUND = 0, 1, 2
 
 
 def fullprover_set_r1cs(fullprover, r1cs_path):
@@ -734,6 +739,36 @@ class R1cs:
         out = np.zeros(96, dtype=np.uint8)
         self.ctx._chk(self.ctx.L.k16_r1cs_last_values(self.h, int(i), _p(out)))
         return tuple(int.from_bytes(out[32 * k:32 * k + 32].tobytes(), "little") for k in range(3))
+
+    def unbound_wires(self, cap=None, status=False):
+        """k16_r1cs_unbound_wires on the sums of the last completed check: (n_absent, n_unbound, wires, classes) with the lowest
+        min(n_absent + n_unbound, cap) wires that are not WIRE_BOUND, ascending, and their WIRE_* classes as uint8; cap=None
+        asks for all of them.  status=True appends the class of every wire (n_wires x uint8)."""
+        n_wires = self.info()["n_wires"]
+        cap = n_wires if cap is None else int(cap)
+        wires, cls = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint8)
+        full = np.zeros(n_wires, dtype=np.uint8) if status else None
+        na, nu = C.c_uint64(), C.c_uint64()
+        self.ctx._chk(self.ctx.L.k16_r1cs_unbound_wires(self.h, C.byref(na), C.byref(nu), _p(wires), _p(cls), cap,
+                                                        _p(full) if status else None))
+        k = min(int(na.value) + int(nu.value), cap)
+        out = (int(na.value), int(nu.value), wires[:k].copy(), cls[:k].copy())
+        return out + (full,) if status else out
+
+    def wire_constraints(self, wire, cap=None):
+        """k16_r1cs_wire_constraints: (n, ndarray of the lowest min(n, cap) constraints the wire has a non-zero merged
+        coefficient in, ascending); cap=None asks for all of them.  Host only."""
+        cap = self.info()["n_constraints"] if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        n = C.c_uint64()
+        self.ctx._chk(self.ctx.L.k16_r1cs_wire_constraints(self.h, int(wire), C.byref(n), _p(out), cap))
+        return int(n.value), out[:min(int(n.value), cap)].copy()
+
+    def incidences(self):
+        """k16_r1cs_incidences: the number of (wire, constraint) pairs with a non-zero merged coefficient."""
+        n = C.c_uint64()
+        self.ctx._chk(self.ctx.L.k16_r1cs_incidences(self.h, C.byref(n)))
+        return int(n.value)
 
     def match_zkey(self, zkey_bytes):
         """k16_r1cs_match_zkey: 0 when the zkey was made from this circuit, else 1 header / 2 A / 3 B / 4 public rows
