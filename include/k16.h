@@ -610,6 +610,32 @@ int  k16_r1cs_unbound_wires(k16_r1cs* r, uint64_t* n_absent, uint64_t* n_unbound
 int  k16_r1cs_wire_constraints(k16_r1cs* r, uint32_t wire, uint64_t* n, uint32_t* h_constraints, uint32_t cap);
 int  k16_r1cs_incidences(k16_r1cs* r, uint64_t* n_pairs);
 
+/* ---- second-value scan: WHICH wires could take exactly one other value? ----
+ * The unbound-wire scan finds the wires that may take ANY value.  This one finds the wires that may take ONE other value with
+ * every other wire held fixed -- the two roots of a square, a boolean that nothing but b (b - 1) = 0 uses.  Such a wire is BOUND
+ * above, yet a second witness satisfies every constraint and its proof verifies.  With lin and quad as above, changing wire i
+ * alone by d moves the residual of constraint c by d lin + d^2 quad, and each (wire, constraint) incidence is
+ *   FREE  lin = 0 and quad = 0: every d leaves the residual as it is
+ *   PIN   exactly one of lin, quad is zero: no d != 0 leaves it (the linear case, and the double root x x = y at x = 0)
+ *   ROOT  lin != 0 and quad != 0: exactly one d != 0 leaves it, d = -lin / quad
+ * A wire is K16_WIRE_TWO_VALUED when it has no PIN incidence, at least one ROOT incidence, and all its ROOT incidences give the
+ * same d: the wire's SHIFT; w_i + d is the second value.  Every other wire keeps its class of the unbound-wire scan, BOUND now
+ * reading "single-valued with respect to changes of one wire".  Wire 0 is BOUND and never listed.  Zero is zero modulo r
+ * (canonical form); the scan is exact and deterministic.  It is a statement about the CHANGE of the residuals: defined for any
+ * witness a check completed on, meant for a satisfying one.  It judges nothing: both roots may be meant.
+ *   k16_r1cs_second_values  on the sums of the last completed check, over the incidence list of the unbound-wire scan (made and
+ *                           uploaded by whichever of the two scans comes first; this scan's own per-wire buffers by its first
+ *                           call).  *n_two_valued: how many wires are two-valued.  h_wires / h_shift (either may be NULL): the
+ *                           lowest min(*n_two_valued, cap) of them, ascending, and their shifts, 32 bytes each: standard form,
+ *                           little-endian, canonical, never zero -- the same bytes on every run.  h_status (may be NULL): n_wires
+ *                           bytes, the class 0 .. 3 of every wire; with 3 read as K16_WIRE_BOUND these are the bytes
+ *                           k16_r1cs_unbound_wires writes for the same sums.
+ * Preconditions, errors and THREADING as k16_r1cs_unbound_wires: K16_ERR_ARG when no check has completed on r or a prove call is
+ * running on it; every error leaves nothing in flight. */
+enum { K16_WIRE_TWO_VALUED = 3 };
+int  k16_r1cs_second_values(k16_r1cs* r, uint64_t* n_two_valued, uint32_t* h_wires, uint8_t* h_shift /* 32 B each */, uint32_t cap,
+                            uint8_t* h_status /* n_wires bytes, may be NULL */);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

@@ -19,12 +19,20 @@
 //   k_r1cs_incidences  one lane per (wire, constraint) incidence: is d(a b - c) / d(wire) or the wire's quadratic part non-zero?
 //                      A wave ORs the bits of the wires it found bound into a mask of ceil(nWires / 64) words; the host reads it.
 // Its list and its buffers are made by the first scan of an object: a circuit that is never scanned pays nothing.
+// The second-value scan (k16_r1cs_second_values) walks the same list for the wires that admit exactly
+// ONE other value with every other wire held fixed:
+//   k_r1cs_kinds   one lane per incidence: PIN (one of lin, quad is zero) or ROOT (neither is)?  Two masks, and per wire the
+//                  lowest ROOT incidence -- the wire's reference
+//   k_r1cs_agree   one lane per incidence: does a ROOT incidence move the wire by the same d = -lin / quad as the reference does?
+//                  Where not, the wire is pinned after all
+//   k_r1cs_shifts  one lane per LISTED wire: d from the reference incidence, one inversion, standard form
 #include <stdio.h>
 #include <string.h>
 #include <memory>
 #include <string>
 #include <vector>
 #include "ctx.h"
+#include "frinv_dev.h"
 #include "r1cs_file.h"
 #include "r1cs_pairs.h"
 #include "spmv_dev.h"
@@ -89,6 +97,41 @@ __global__ void __launch_bounds__(256) k_r1cs_judge(const Fr* __restrict__ rows,
     if ((threadIdx.x & 63u) == 0 && (i >> 6) < n_words) mask[i >> 6] = votes;
 }
 
+// The runs of neighbouring lanes of a wave that hold the same key (here: the same mask word, or the same wire -- the list is
+// ordered by wire).  first: the first lane of my run, last: I am its last lane.  Needs the whole wave.
+struct WaveRun {
+    uint32_t           first;
+    bool               last;
+    unsigned long long below; // the lanes of my run before me
+};
+__device__ __forceinline__ WaveRun wave_run(uint32_t key)
+{
+    const uint32_t           lane  = threadIdx.x & 63u;
+    const uint32_t           prev  = __shfl_up(key, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || key != prev);               // first lane of each run (bit 0 is set)
+    const unsigned long long upto  = lane == 63u ? ~0ull : (1ull << (lane + 1)) - 1;   // lanes 0 .. lane
+    WaveRun                  r;
+    r.first = 63u - (uint32_t)__clzll((long long)(heads & upto));
+    r.last  = lane == 63u || ((heads >> (lane + 1)) & 1ull) != 0;
+    r.below = (upto >> 1) & ~((1ull << r.first) - 1);
+    return r;
+}
+// mask[word] |= the OR of `bits` over each run of lanes that share `word` (a segmented inclusive scan upwards; the run's last lane
+// stores).  The mask was cleared before the launch and bits are only ever set: a read that lags behind can only miss bits that
+// are set by now -- the atomic is then issued for nothing, the mask is the same.  Other lanes update the word atomically, so the
+// read is a relaxed atomic load and `mask` is no __restrict__ pointer: the compiler may not hoist or merge it.
+__device__ __forceinline__ void wave_or_into(unsigned long long* mask, uint32_t word, unsigned long long bits)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const WaveRun  run  = wave_run(word);
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const unsigned long long up = __shfl_up(bits, d, 64);
+        if (lane >= run.first + d) bits |= up;
+    }
+    if (run.last && bits && (__atomic_load_n(&mask[word], __ATOMIC_RELAXED) & bits) != bits) atomicOr(&mask[word], bits);
+}
+
 // The unbound-wire scan.  Change wire i alone by d: the residual a_c b_c - c_c of constraint c moves by d lin + d^2 quad with
 //   lin = A^ b_c + B^ a_c - C^,  quad = A^ B^      (A^, B^, C^: the merged coefficients of wire i in constraint c)
 // and the wire is bound by c when lin != 0 or quad != 0 (mod r).
@@ -114,10 +157,9 @@ __global__ void __launch_bounds__(256) k_r1cs_incidences(const uint4* __restrict
                                                          const Fr* __restrict__ side, const Fr* __restrict__ rows, uint32_t M,
                                                          unsigned long long* bound)
 {
-    const uint32_t i    = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t       w    = 0xffffffffu; // (no wire: the lanes behind the list)
-    bool           hit  = false;
+    const uint32_t i   = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t       w   = 0xffffffffu; // (no wire: the lanes behind the list)
+    bool           hit = false;
     if (i < n_pairs) {
         const uint4 e = inc[i]; // x: constraint, y / z / w: positions of A^ / B^ / C^
         w             = wire[i];
@@ -133,23 +175,130 @@ __global__ void __launch_bounds__(256) k_r1cs_incidences(const uint4* __restrict
             hit        = (d.v[0] | d.v[1] | d.v[2] | d.v[3] | d.v[4] | d.v[5] | d.v[6] | d.v[7]) != 0;
         }
     }
-    // OR of the hits of each run of lanes that share a mask word (a segmented inclusive scan upwards); its last lane stores
-    const uint32_t           word  = w >> 6;
-    const uint32_t           prev  = __shfl_up(word, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || word != prev); // first lane of each run (bit 0 is set)
-    const unsigned long long upto  = lane == 63u ? ~0ull : (1ull << (lane + 1)) - 1;     // lanes 0 .. lane
-    const uint32_t           first = 63u - (uint32_t)__clzll((long long)(heads & upto)); // my run's first lane
-    unsigned long long       bits  = hit ? 1ull << (w & 63u) : 0ull;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const unsigned long long up = __shfl_up(bits, d, 64);
-        if (lane >= first + d) bits |= up;
+    wave_or_into(bound, w >> 6, hit ? 1ull << (w & 63u) : 0ull);
+}
+
+// The second-value scan.  With lin and quad as above, an incidence is FREE (lin = quad = 0: every d
+// leaves the residual), a PIN (exactly one of them is zero: no d != 0 leaves it -- d lin = 0 or d^2 quad = 0 has the root 0
+// alone, r being prime) or a ROOT (neither is zero: d lin + d^2 quad = 0 has exactly one other root, d = -lin / quad).  A wire
+// is TWO-VALUED when it has no PIN, at least one ROOT, and all its ROOTs give the same d.
+// Scalings, with coefficients k 2^522, sums s 2^261 and frmul9 dividing by 2^261 as above:
+//   lin   frmul9(A^ 2^522, b 2^261) + frmul9(B^ 2^522, a 2^261) - C^ 2^522  =  lin 2^522 -- here BOTH of A^, B^ can be there: two
+//         products, fradd9 of two values < 2r (its bound is < 4r), then frsub9 with the subtrahend C^ 2^522 < r (its bound is < 2r)
+//   quad  frmul9(A^ 2^522, B^ 2^522) = quad 2^783; coefficients < r: the product is < 2r.  quad != 0 exactly when the incidence
+//         names both A^ and B^ (see above): the kind needs no product, the comparison and the shift do
+//   two ROOTs (lin, quad), (lin0, quad0) give the same d exactly when lin quad0 = lin0 quad (quad, quad0 != 0):
+//         frmul9(lin 2^522, quad0 2^783) and frmul9(lin0 2^522, quad 2^783) both carry 2^1044; operands < 2r, products < 2r, and
+//         the difference goes through fr9_to_standard: products of coefficients like r - 1 agree only modulo r
+//   d     frmul9(quad 2^783, 1) = quad 2^522 = (quad 2^261) 2^261, the R' value of quad 2^261; frinv9 returns the R' value of
+//         its inverse, quad^-1 2^-261 2^261 = quad^-1 with factor 1; frmul9(lin 2^522, quad^-1) = (lin / quad) 2^261, an R' value
+//         again, negated by frsub9(0, .) -- and fr9_to_standard divides by 2^261: the canonical -lin / quad.
+struct IncTerms {
+    Fr9  lin;
+    bool has_quad; // both A^ and B^ are there: quad != 0
+};
+// lin 2^522 of incidence e (x: constraint, y / z / w: positions of A^ / B^ / C^)
+__device__ __forceinline__ IncTerms inc_terms(const uint4 e, const Fr* __restrict__ coef, uint32_t n_entries,
+                                              const Fr* __restrict__ side, const Fr* __restrict__ rows, uint32_t M)
+{
+    auto     at = [&](uint32_t p) { return ld_r9(p < n_entries ? &coef[p] : &side[p - n_entries]); };
+    IncTerms t;
+    t.lin      = fq9_zero();
+    t.has_quad = e.y != R1CS_PAIR_NONE && e.z != R1CS_PAIR_NONE;
+    if (e.y != R1CS_PAIR_NONE) t.lin = frmul9(at(e.y), ld_r9(&rows[(size_t)M + e.x]));
+    if (e.z != R1CS_PAIR_NONE) {
+        const Fr9 ba = frmul9(at(e.z), ld_r9(&rows[e.x]));
+        t.lin        = e.y != R1CS_PAIR_NONE ? fradd9(t.lin, ba) : ba;
     }
-    const bool last = lane == 63u || ((heads >> (lane + 1)) & 1ull) != 0;
-    // (the mask was cleared before the launch and bits are only ever set: a read that lags behind can only miss bits that are
-    // set by now -- the atomic is then issued for nothing, the mask is the same.  Other lanes update the word atomically, so
-    // the read is a relaxed atomic load and `bound` is no __restrict__ pointer: the compiler may not hoist or merge it)
-    if (last && bits && (__atomic_load_n(&bound[word], __ATOMIC_RELAXED) & bits) != bits) atomicOr(&bound[word], bits);
+    if (e.w != R1CS_PAIR_NONE) t.lin = frsub9(t.lin, at(e.w));
+    return t;
+}
+// quad 2^783 of an incidence that names both
+__device__ __forceinline__ Fr9 inc_quad(const uint4 e, const Fr* __restrict__ coef, uint32_t n_entries, const Fr* __restrict__ side)
+{
+    auto at = [&](uint32_t p) { return ld_r9(p < n_entries ? &coef[p] : &side[p - n_entries]); };
+    return frmul9(at(e.y), at(e.z));
+}
+__device__ __forceinline__ bool fr9_nonzero(const Fr9& x)
+{
+    const Fr d = fr9_to_standard(x);
+    return (d.v[0] | d.v[1] | d.v[2] | d.v[3] | d.v[4] | d.v[5] | d.v[6] | d.v[7]) != 0;
+}
+
+// pinned / rooted: ceil(n_wires / 64) words each, cleared before the launch: bit i = wire i has a PIN / a ROOT incidence,
+// merged per word and wave as in k_r1cs_incidences.  ref[n_wires], all ones before the launch: the lowest ROOT incidence of each
+// wire.  The list is ordered by wire and, within a wire, ascending: among the lanes of a wave that share a wire the FIRST ROOT
+// lane holds the wave's minimum, it alone issues the atomicMin, and only where ref does not show an index that low yet (ref only
+// ever falls: a read that lags behind costs an atomic for nothing).  One atomic per wire and wave at the most, however long the
+// column; a minimum is the same whatever order the lanes run in.  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_kinds(const uint4* __restrict__ inc, const uint32_t* __restrict__ wire,
+                                                    uint32_t n_pairs, const Fr* __restrict__ coef, uint32_t n_entries,
+                                                    const Fr* __restrict__ side, const Fr* __restrict__ rows, uint32_t M,
+                                                    unsigned long long* pinned, unsigned long long* rooted, uint32_t* ref)
+{
+    const uint32_t i   = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t       w   = 0xffffffffu; // (no wire: the lanes behind the list)
+    bool           pin = false, root = false;
+    if (i < n_pairs) {
+        w                 = wire[i];
+        const IncTerms t  = inc_terms(inc[i], coef, n_entries, side, rows, M);
+        const bool     nz = fr9_nonzero(t.lin);
+        pin               = nz != t.has_quad;
+        root              = nz && t.has_quad;
+    }
+    const unsigned long long bit = 1ull << (w & 63u);
+    wave_or_into(pinned, w >> 6, pin ? bit : 0ull);
+    wave_or_into(rooted, w >> 6, root ? bit : 0ull);
+    const WaveRun            run   = wave_run(w);
+    const unsigned long long roots = __ballot(root);
+    if (root && (roots & run.below) == 0 && __atomic_load_n(&ref[w], __ATOMIC_RELAXED) > i) atomicMin(&ref[w], i);
+}
+
+// A ROOT incidence other than its wire's reference: lin quad0 = lin0 quad?  Where not, the two move the wire to different
+// values and the wire's bit is set in `pinned` (no single d != 0 serves both).  Equality with ONE reference is equality of all
+// the d of a wire, since every quad is non-zero.  Nothing per incidence is kept between the kernels: the reference's terms are
+// formed again, two products.  Launched with whole waves, after k_r1cs_kinds on the same stream.
+__global__ void __launch_bounds__(256) k_r1cs_agree(const uint4* __restrict__ inc, const uint32_t* __restrict__ wire,
+                                                    uint32_t n_pairs, const Fr* __restrict__ coef, uint32_t n_entries,
+                                                    const Fr* __restrict__ side, const Fr* __restrict__ rows, uint32_t M,
+                                                    const uint32_t* __restrict__ ref, unsigned long long* pinned)
+{
+    const uint32_t i     = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t       w     = 0xffffffffu;
+    bool           clash = false;
+    if (i < n_pairs) {
+        w             = wire[i];
+        const uint4 e = inc[i];
+        const uint32_t j = ref[w];
+        if (e.y != R1CS_PAIR_NONE && e.z != R1CS_PAIR_NONE && j != i && j < n_pairs) {
+            const IncTerms t = inc_terms(e, coef, n_entries, side, rows, M);
+            if (fr9_nonzero(t.lin)) {
+                const uint4    e0 = inc[j];
+                const IncTerms t0 = inc_terms(e0, coef, n_entries, side, rows, M);
+                clash = fr9_nonzero(frsub9(frmul9(t.lin, inc_quad(e0, coef, n_entries, side)), frmul9(t0.lin, inc_quad(e, coef, n_entries, side))));
+            }
+        }
+    }
+    wave_or_into(pinned, w >> 6, clash ? 1ull << (w & 63u) : 0ull);
+}
+
+// list[n]: two-valued wires; shift[k] = -lin0 / quad0 of list[k]'s reference incidence, standard form (canonical; non-zero, as
+// lin0 != 0).  One inversion per lane: the work is the list's, not the circuit's.
+__global__ void __launch_bounds__(64) k_r1cs_shifts(const uint32_t* __restrict__ list, uint32_t n, const uint4* __restrict__ inc,
+                                                    uint32_t n_pairs, const Fr* __restrict__ coef, uint32_t n_entries,
+                                                    const Fr* __restrict__ side, const Fr* __restrict__ rows, uint32_t M,
+                                                    const uint32_t* __restrict__ ref, Fr* __restrict__ shift)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t j = ref[list[k]];
+    if (j >= n_pairs) return; // (a listed wire has a ROOT incidence)
+    const uint4    e0 = inc[j];
+    const IncTerms t0 = inc_terms(e0, coef, n_entries, side, rows, M);
+    Fr9            one = fq9_zero();
+    one.l[0]           = 1;
+    const Fr9 qinv = frinv9(frmul9(inc_quad(e0, coef, n_entries, side), one));
+    st_fr(&shift[k], fr9_to_standard(frsub9(fq9_zero(), frmul9(t0.lin, qinv))));
 }
 
 // What a prove call keeps of its check (pinned, device-mapped; read by the host after the check is joined).
@@ -234,6 +383,12 @@ struct k16_r1cs {
     Fr*                        d_side    = nullptr; // merged sums * 2^522 mod r
     unsigned long long *       d_bound = nullptr, *h_bound = nullptr; // [ceil(n_wires / 64)], device / pinned
     bool                       scan_ready = false;
+    // the second-value scan, on top of the list above: made by its first call, kept until the object goes
+    unsigned long long *d_kinds = nullptr, *h_kinds = nullptr; // pinned | rooted, [ceil(n_wires / 64)] each, device / pinned
+    uint32_t*           d_ref   = nullptr;                     // [n_wires] the lowest ROOT incidence of each wire
+    uint32_t *          d_list = nullptr, *h_list = nullptr;   // [n_wires] the listed wires, device / pinned
+    Fr*                 d_shift = nullptr;                     // [n_wires] their shifts, standard form
+    bool                second_ready = false;
 };
 
 void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const R1csFile** file)
@@ -253,10 +408,22 @@ static void r1cs_scan_free(k16_r1cs* r)
     r->scan_ready = false;
 }
 
+static void r1cs_second_free(k16_r1cs* r)
+{
+    void* bufs[] = {r->d_kinds, r->d_ref, r->d_list, r->d_shift};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (r->h_kinds) (void)hipHostFree(r->h_kinds);
+    if (r->h_list) (void)hipHostFree(r->h_list);
+    r->d_kinds = nullptr, r->h_kinds = nullptr, r->d_ref = nullptr, r->d_list = nullptr, r->h_list = nullptr, r->d_shift = nullptr;
+    r->second_ready = false;
+}
+
 static void r1cs_free(k16_r1cs* r)
 {
     if (!r) return;
     if (r->ctx) (void)hipSetDevice(r->ctx->device);
+    r1cs_second_free(r);
     r1cs_scan_free(r);
     void* bufs[] = {r->d_slices, r->d_longs, r->d_rowof, r->d_wire, r->d_coef, r->d_wtns, r->d_n16, r->d_rows, r->d_mask};
     for (void* b : bufs)
@@ -690,6 +857,109 @@ extern "C" int k16_r1cs_unbound_wires(k16_r1cs* r, uint64_t* n_absent, uint64_t*
     }
     *n_absent  = absent;
     *n_unbound = unbound;
+    return K16_OK;
+    });
+}
+
+// ---- the second-value scan
+// masks, references, list and shifts, by the first call; the incidence list itself is the unbound-wire scan's
+static int r1cs_second_alloc(k16_ctx* ctx, k16_r1cs* r)
+{
+    const size_t words = r->pairs->present.size(), n = r->n_wires;
+    int          rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_kinds, 2 * words * 8))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_ref, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_list, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_shift, n * 32))) return rc;
+    K16_HIP(ctx, hipHostMalloc((void**)&r->h_kinds, std::max<size_t>(2 * words * 8, 8), hipHostMallocDefault));
+    K16_HIP(ctx, hipHostMalloc((void**)&r->h_list, std::max<size_t>(n * 4, 8), hipHostMallocDefault));
+    r->second_ready = true;
+    return K16_OK;
+}
+
+static int r1cs_second_run(k16_ctx* ctx, k16_r1cs* r, uint64_t* n_two_valued, uint32_t* h_wires, uint8_t* h_shift, uint32_t cap,
+                           uint8_t* h_status)
+{
+    const R1csPairs& P     = *r->pairs;
+    const uint32_t   n     = (uint32_t)P.pair.size() - P.start[1]; // all but wire 0's column
+    const size_t     words = P.present.size();
+    const dim3       grid((unsigned)(((uint64_t)n + 255) / 256));
+    hipStream_t      st = ctx->stream;
+    K16_HIP(ctx, hipMemsetAsync(r->d_kinds, 0, 2 * words * 8, st));
+    K16_HIP(ctx, hipMemsetAsync(r->d_ref, 0xff, (size_t)r->n_wires * 4, st));
+    if (n) {
+        {
+            k16_stat_scope sc(ctx, "r1cs_kinds", st);
+            hipLaunchKernelGGL(k_r1cs_kinds, grid, dim3(256), 0, st, r->d_inc, r->d_incwire, n, r->d_coef, P.n_entries, r->d_side,
+                               r->d_rows, r->M, r->d_kinds, r->d_kinds + words, r->d_ref);
+        }
+        {
+            k16_stat_scope sc(ctx, "r1cs_agree", st);
+            hipLaunchKernelGGL(k_r1cs_agree, grid, dim3(256), 0, st, r->d_inc, r->d_incwire, n, r->d_coef, P.n_entries, r->d_side,
+                               r->d_rows, r->M, r->d_ref, r->d_kinds);
+        }
+    }
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(r->h_kinds, r->d_kinds, 2 * words * 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    const unsigned long long *pinned = r->h_kinds, *rooted = r->h_kinds + words;
+    const bool                want_list = (h_wires || h_shift) && cap;
+    uint64_t                  count = 0;
+    uint32_t                  listed = 0;
+    for (size_t w = 0; w < words; w++) {
+        const uint32_t     in_word = (uint32_t)std::min<uint64_t>(64, (uint64_t)r->n_wires - 64 * (uint64_t)w);
+        unsigned long long valid   = in_word == 64 ? ~0ull : (1ull << in_word) - 1;
+        if (w == 0) valid &= ~1ull; // wire 0 is the constant
+        // bound as k_r1cs_incidences finds it: lin != 0 or quad != 0 somewhere, a PIN or a ROOT (a clash is among ROOTs)
+        const unsigned long long free_ = ~(pinned[w] | rooted[w]) & valid, here = P.present[w], two = rooted[w] & ~pinned[w] & valid;
+        count += (uint64_t)__builtin_popcountll(two);
+        if (h_status)
+            for (uint32_t b = 0; b < in_word; b++)
+                h_status[64 * w + b] = (two >> b) & 1    ? K16_WIRE_TWO_VALUED
+                                       : (free_ >> b) & 1 ? ((here >> b) & 1 ? K16_WIRE_UNBOUND : K16_WIRE_ABSENT)
+                                                          : K16_WIRE_BOUND;
+        for (unsigned long long m = two; m && listed < cap && want_list; m &= m - 1) r->h_list[listed++] = (uint32_t)(64 * w + (uint32_t)__builtin_ctzll(m));
+    }
+    *n_two_valued = count;
+    if (h_wires && listed) memcpy(h_wires, r->h_list, (size_t)listed * 4);
+    if (h_shift && listed) {
+        K16_HIP(ctx, hipMemcpyAsync(r->d_list, r->h_list, (size_t)listed * 4, hipMemcpyHostToDevice, st));
+        {
+            k16_stat_scope sc(ctx, "r1cs_shifts", st);
+            hipLaunchKernelGGL(k_r1cs_shifts, dim3((listed + 63) / 64), dim3(64), 0, st, r->d_list, listed, r->d_inc, n, r->d_coef,
+                               P.n_entries, r->d_side, r->d_rows, r->M, r->d_ref, r->d_shift);
+        }
+        K16_HIP(ctx, hipGetLastError());
+        K16_HIP(ctx, hipMemcpyAsync(h_shift, r->d_shift, (size_t)listed * 32, hipMemcpyDeviceToHost, st));
+        K16_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_second_values(k16_r1cs* r, uint64_t* n_two_valued, uint32_t* h_wires, uint8_t* h_shift, uint32_t cap,
+                                      uint8_t* h_status)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_two_valued) return K16_ERR_ARG;
+    *n_two_valued = 0;
+    k16_ctx* ctx  = r->ctx;
+    if (!r->have_values || r->forked_on) {
+        ctx->err = "no completed check to scan";
+        return K16_ERR_ARG;
+    }
+    int rc = r1cs_pairs_get(ctx, r);
+    if (rc) return rc;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    if (!r->scan_ready) rc = r1cs_scan_upload(ctx, r);
+    if (!rc && !r->second_ready) rc = r1cs_second_alloc(ctx, r);
+    if (!rc) rc = r1cs_second_run(ctx, r, n_two_valued, h_wires, h_shift, cap, h_status);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream); // nothing of the scan stays in flight
+        if (!r->second_ready) r1cs_second_free(r);
+        if (!r->scan_ready) r1cs_scan_free(r);
+        *n_two_valued = 0;
+        return rc;
+    }
     return K16_OK;
     });
 }

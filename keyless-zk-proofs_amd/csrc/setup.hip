@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 #include "ctx.h"
+#include "frinv_dev.h"
 #include "setup_plan.h"
 #include "spmv_dev.h"
 
@@ -33,26 +34,6 @@ constexpr unsigned GENMUL_CHUNK[2] = {8, 2};  // points per lane and inversion
 constexpr uint64_t GENMUL_BATCH[2] = {1ull << 21, 1ull << 20}; // points per launch (bounds the scratch area: 302 MB)
 constexpr unsigned LAG_CHUNK       = 16;
 constexpr unsigned genmul_windows(int group) { return (256 + GENMUL_W[group] - 1) / GENMUL_W[group]; }
-
-__device__ __forceinline__ Fr9 fr9_one()
-{
-    Fr9 r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = Fr9C::ONE[i];
-    return r;
-}
-// a^(r-2) in the R' domain; a < 2r, a != 0 mod r
-__device__ __noinline__ Fr9 frinv9(const Fr9& a)
-{
-    Fr9 r = fr9_one();
-#pragma clang loop unroll(disable)
-    for (int bit = 253; bit >= 0; bit--) {
-        const uint32_t e = FrParams::P[bit >> 5] - (bit < 32 ? 2u : 0u); // r - 2: the low word is 0xf0000001, no borrow
-        r = frmul9(r, r);
-        if ((e >> (bit & 31)) & 1u) r = frmul9(r, a);
-    }
-    return r;
-}
 
 struct LagArgs {
     Fr t, c, omega, omega_inv; // packed R': the point, (t^N - 1) / N, the domain's generator and its inverse

@@ -48,7 +48,7 @@ SYMBOLS = [
     "k16_prover_prove_compact_verified", "k16_prover_prove_file_verified", "k16_verify_split_gt", "k16_fullprover_set_verify",
     "k16_r1cs_create", "k16_r1cs_create_mem", "k16_r1cs_destroy", "k16_r1cs_info", "k16_r1cs_check_mem", "k16_r1cs_check_file",
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
-    "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences",
+    "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences", "k16_r1cs_second_values",
     "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
@@ -177,6 +177,7 @@ def load():
     L.k16_r1cs_unbound_wires.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), vp, vp, u32, vp]
     L.k16_r1cs_wire_constraints.argtypes = [vp, u32, C.POINTER(u64), vp, u32]
     L.k16_r1cs_incidences.argtypes = [vp, C.POINTER(u64)]
+    L.k16_r1cs_second_values.argtypes = [vp, C.POINTER(u64), vp, vp, u32, vp]
     L.k16_prover_set_r1cs.argtypes = [vp, vp]
     L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
     L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
@@ -528,7 +529,7 @@ def points_sum(group, parts):
 # k16_prover_last_check / k16_fullprover_last_rejection (include/k16.h)
 R1CS_REPORT_MAX = 64
 CHECK_NONE, CHECK_SATISFIED, CHECK_BROKEN, CHECK_WITNESS_REFUSED = 0, 1, 2, 3
-WIRE_BOUND, WIRE_ABSENT, WIRE_UNBOUND = 0, 1, 2
+WIRE_BOUND, WIRE_ABSENT, WIRE_UNBOUND, WIRE_TWO_VALUED = 0, 1, 2, 3
 
 
 def fullprover_set_r1cs(fullprover, r1cs_path):
@@ -753,6 +754,20 @@ class R1cs:
                                                         _p(full) if status else None))
         k = min(int(na.value) + int(nu.value), cap)
         out = (int(na.value), int(nu.value), wires[:k].copy(), cls[:k].copy())
+        return out + (full,) if status else out
+
+    def second_values(self, cap=None, status=False):
+        """k16_r1cs_second_values on the sums of the last completed check: (n, wires, shifts) with the lowest min(n, cap) wires
+        that are WIRE_TWO_VALUED, ascending, and their shifts as Python ints (wire + shift mod r is the second value); cap=None
+        asks for all of them.  status=True appends the class 0 .. 3 of every wire (n_wires x uint8)."""
+        n_wires = self.info()["n_wires"]
+        cap = n_wires if cap is None else int(cap)
+        wires, shifts = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros((max(cap, 1), 32), dtype=np.uint8)
+        full = np.zeros(n_wires, dtype=np.uint8) if status else None
+        n = C.c_uint64()
+        self.ctx._chk(self.ctx.L.k16_r1cs_second_values(self.h, C.byref(n), _p(wires), _p(shifts), cap, _p(full) if status else None))
+        k = min(int(n.value), cap)
+        out = (int(n.value), wires[:k].copy(), [int.from_bytes(shifts[i].tobytes(), "little") for i in range(k)])
         return out + (full,) if status else out
 
     def wire_constraints(self, wire, cap=None):
