@@ -636,6 +636,43 @@ enum { K16_WIRE_TWO_VALUED = 3 };
 int  k16_r1cs_second_values(k16_r1cs* r, uint64_t* n_two_valued, uint32_t* h_wires, uint8_t* h_shift /* 32 B each */, uint32_t cap,
                             uint8_t* h_status /* n_wires bytes, may be NULL */);
 
+/* ---- determinism closure: WHICH wires do the inputs leave open? ----
+ * Both scans above move ONE wire with every other wire held fixed.  This call asks the question of an audit: given the values of
+ * the SEED wires (by default the circuit's inputs), is every other wire forced?  With FREE / PIN / ROOT of an incidence as
+ * above, the closure K is the least set of wires that holds the seed S (wire 0 always) and satisfies
+ *     constraint c was not found broken by the last check, exactly one wire x with a non-zero merged coefficient in c lies
+ *     outside K, and the incidence (x, c) is a PIN   ==>   x is in K
+ * taken level by level: K_0 = S, K_k+1 = K_k and every x the rule gives with respect to K_k.  The ROUND of a derived wire is the
+ * first k with x in K_k, its BY constraint the lowest c the rule holds for with respect to K_(round - 1).  Both are functions of
+ * circuit, witness and seed alone; the call is exact and deterministic.
+ * SOUND: a witness that satisfies the circuit and agrees with this one on S agrees with it on K (in c all wires but x are equal,
+ * the residuals differ by t lin + t^2 quad, both are 0, a PIN leaves t = 0).  Hence: a broken constraint derives nothing; a FREE
+ * incidence of a second outside wire still counts (two outside wires have a cross term neither's lin or quad shows); a ROOT
+ * derives nothing (the two-valued case).  NOT COMPLETE: an OPEN wire may still be forced by an argument over several constraints.
+ *   K16_DET_SEED     in S
+ *   K16_DET_DERIVED  in K, not in S
+ *   K16_DET_ABSENT   not in K and in no term (structural, as K16_WIRE_ABSENT)
+ *   K16_DET_OPEN     not in K and in some term
+ * It judges nothing: an OPEN wire behind a zero selector is legitimate; an OPEN public output is the finding to look at first.
+ * Defined for any witness a check completed on, meant for a satisfying one.
+ *   h_seed / n_seed   the seed wires; duplicates are legal, wire 0 is added, a wire >= nWires is K16_ERR_ARG before anything is
+ *                     launched.  NULL: wire 0 and the wires nPubOut + 1 .. nPubOut + nPubIn + nPrvIn of the .r1cs header (iden3
+ *                     wire order); K16_ERR_ARG when the header's counts reach beyond nWires.
+ *   *n_derived, *n_absent, *n_open   wires per class;  *n_rounds   the highest round used
+ *   h_wires (may be NULL)   the lowest min(*n_open, cap) OPEN wires, ascending
+ *   h_status (may be NULL)  n_wires bytes, the class of every wire
+ *   h_round (may be NULL)   n_wires words: 0 for a seed wire, k >= 1 for a derived one, 0xffffffff otherwise
+ *   h_by (may be NULL)      n_wires words: the deriving constraint, 0xffffffff where there is none
+ * One pair of launches and one host synchronise per round (csrc/r1cs_check.hip): a circuit of depth D costs D of them.  The
+ * incidence list is the scans' (made and uploaded by whichever call comes first), this call's own buffers are made by its first
+ * call and stay with the object.  Preconditions, errors and THREADING as k16_r1cs_unbound_wires: K16_ERR_ARG when no check has
+ * completed on r or a prove call is running on it; legal between prove calls on an attached object; every error leaves nothing
+ * in flight. */
+enum { K16_DET_SEED = 0, K16_DET_DERIVED = 1, K16_DET_ABSENT = 2, K16_DET_OPEN = 3 };
+int  k16_r1cs_determined_wires(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_seed, uint64_t* n_derived, uint64_t* n_absent,
+                               uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
+                               uint32_t* h_round, uint32_t* h_by);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

@@ -26,6 +26,9 @@
 //   k_r1cs_agree   one lane per incidence: does a ROOT incidence move the wire by the same d = -lin / quad as the reference does?
 //                  Where not, the wire is pinned after all
 //   k_r1cs_shifts  one lane per LISTED wire: d from the reference incidence, one inversion, standard form
+// The determinism closure (k16_r1cs_determined_wires) asks the global question the two scans leave open:
+// given the values of the seed wires (by default the circuit's inputs), which other wires does the circuit force?  A fixed point
+// over the same list, a round at a time: k_r1cs_det_init / _first / _derive / _expand, described where they stand.
 #include <stdio.h>
 #include <string.h>
 #include <memory>
@@ -301,6 +304,186 @@ __global__ void __launch_bounds__(64) k_r1cs_shifts(const uint32_t* __restrict__
     st_fr(&shift[k], fr9_to_standard(frsub9(fq9_zero(), frmul9(t0.lin, qinv))));
 }
 
+// The determinism closure (k16_r1cs_determined_wires): the least set K of wires that holds the seed and
+// is closed under
+//     constraint c is not broken, exactly ONE wire x with a non-zero merged coefficient in c lies outside K, and the
+//     incidence (x, c) is a PIN  ==>  x joins K
+// computed level by level (K_0 = seed, K_k+1 = K_k and what the rule gives with respect to K_k): round[x] is the first level
+// that holds x, by[x] the lowest constraint that gave it there.  Any witness that satisfies the circuit and agrees with this one
+// on the seed agrees with it on K: in c every wire but x is equal, so the residuals differ by t lin + t^2 quad, both residuals
+// are 0, and a PIN leaves t = 0 alone.  Three details of the rule carry that argument -- none of them is an inefficiency:
+//   a BROKEN constraint derives nothing     its residual under this witness is not 0, the difference says nothing about t
+//   a FREE incidence of an outside wire still COUNTS as an outside wire     two outside wires x, y move the residual by a cross
+//                                           term dx dy (A^x B^y + A^y B^x) that neither wire's lin or quad shows
+//   a ROOT derives nothing                  t = -lin / quad is the second solution: the two-valued case
+// Each constraint carries two words: cnt[c], the number of its incidences (of the device list: wire 0, always in K, is not on
+// it) whose wire lies outside K, and xr[c], the XOR of those incidences' indices -- where cnt is 1, xr IS the one outside
+// incidence.  No constraint-ordered copy of the list is needed.
+//   k_r1cs_det_init    one lane per incidence: a wire outside the seed counts into cnt / xr of its constraint
+//   k_r1cs_det_first   one lane per constraint: cnt = 1 -> the candidate list
+//   k_r1cs_det_derive  one lane per candidate of this round: not broken, cnt still 1 (a constraint may have fallen on to 0 in
+//                      the expansion that listed it), the outside incidence a PIN -> atomicMin(by[x], c); the lane that found
+//                      by[x] empty appends x to the frontier.  `known` is only read here, so by[x] ends as the minimum over
+//                      exactly the constraints that qualify with respect to the level before
+//   k_r1cs_det_expand  one lane per frontier wire: known bit, round[x], and for each incidence of its column cnt[c] -= 1,
+//                      xr[c] ^= index; the lane that saw cnt fall from 2 to 1 appends c to the candidates -- once per
+//                      constraint, cnt only ever falls.  A column of up to DET_SHORT incidences is walked by its lane, a longer
+//                      one by the whole wave, 64 incidences a step: no lane's work grows with a column's length.
+// Both lists only grow: every constraint becomes a candidate at most once and is judged once (its kind depends on the witness
+// alone: a candidate that is no PIN now never is), every wire enters the frontier at most once; a round is a range of each.  The
+// host reads both list sizes once per round from a record in pinned, device-mapped memory, written by the last workgroup of
+// k_r1cs_det_first / _expand to finish (a ticket per workgroup; nothing waits).  Appends are one atomicAdd per wave and list.
+// The order inside a list is arbitrary and nothing observable depends on it: masks are ORs, by is a minimum, round has one value
+// per wire, cnt is a sum and xr an XOR, the sizes are sums.
+constexpr uint32_t DET_NONE  = 0xffffffffu;
+constexpr uint32_t DET_SHORT = 8;
+constexpr uint32_t DET_GRID  = 512; // workgroups of a kernel that ends in det_publish
+struct DetState {
+    uint32_t n_front, n_cand; // sizes of the two lists
+    uint32_t done, pad;       // workgroups of the running kernel that have finished
+};
+struct DetRecord {
+    uint32_t n_front, n_cand;
+};
+
+// list[*total ...] <- value of the lanes that `have` one: one atomicAdd per wave.  Needs the whole wave.  cap: the list's room
+// (every constraint / wire is appended once at the most, so it is never reached).
+__device__ __forceinline__ void wave_append(uint32_t* __restrict__ list, uint32_t* total, uint32_t cap, bool have, uint32_t value)
+{
+    const unsigned long long votes = __ballot(have);
+    if (!votes) return;
+    const uint32_t lane   = threadIdx.x & 63u;
+    const int      leader = __ffsll((long long)votes) - 1;
+    uint32_t       base   = 0;
+    if ((int)lane == leader) base = atomicAdd(total, (uint32_t)__popcll(votes));
+    base               = __shfl(base, leader, 64);
+    const uint32_t pos = base + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
+    if (have && pos < cap) list[pos] = value;
+}
+// The last workgroup to get here copies the list sizes into the host's record.  Every lane of the workgroup calls it, after its
+// last append.
+__device__ __forceinline__ void det_publish(DetState* st, DetRecord* rec)
+{
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    __threadfence(); // this workgroup's appends before its ticket
+    if (atomicAdd(&st->done, 1u) != gridDim.x - 1) return;
+    __threadfence(); // every other workgroup's ticket before the reads
+    rec->n_front = __atomic_load_n(&st->n_front, __ATOMIC_RELAXED);
+    rec->n_cand  = __atomic_load_n(&st->n_cand, __ATOMIC_RELAXED);
+    st->done     = 0; // (the next launch on the stream starts behind this kernel)
+}
+__device__ __forceinline__ bool det_bit(const unsigned long long* __restrict__ mask, uint32_t i) { return (mask[i >> 6] >> (i & 63u)) & 1ull; }
+
+// cnt / xr: M words each, cleared before the launch.  seed: ceil(n_wires / 64) words.
+__global__ void __launch_bounds__(256) k_r1cs_det_init(const uint4* __restrict__ inc, const uint32_t* __restrict__ wire,
+                                                       uint32_t n_pairs, uint32_t n_wires, uint32_t M,
+                                                       const unsigned long long* __restrict__ seed, uint32_t* cnt, uint32_t* xr)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pairs) return;
+    const uint32_t w = wire[i], c = inc[i].x;
+    if (w >= n_wires || c >= M || det_bit(seed, w)) return;
+    atomicAdd(&cnt[c], 1u);
+    atomicXor(&xr[c], i);
+}
+
+// Launched with whole waves, DET_GRID workgroups at the most: a workgroup strides the constraints (every workgroup draws a ticket
+// in det_publish, on ONE counter: a ticket per 256 constraints would cost more than the pass).
+__global__ void __launch_bounds__(256) k_r1cs_det_first(const uint32_t* __restrict__ cnt, uint32_t M, uint32_t* __restrict__ cand,
+                                                        DetState* st, DetRecord* rec)
+{
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < M; base += (uint64_t)gridDim.x * 256u) { // (the same trips for a whole workgroup)
+        const uint64_t c = base + threadIdx.x;
+        wave_append(cand, &st->n_cand, M, c < M && cnt[c] == 1u, (uint32_t)c);
+    }
+    det_publish(st, rec);
+}
+
+// cand[0 .. n): the candidates of this round.  verdict: the check's mask (bit c: constraint c is broken).  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_det_derive(const uint32_t* __restrict__ cand, uint32_t n, const uint4* __restrict__ inc,
+                                                         const uint32_t* __restrict__ wire, uint32_t n_pairs,
+                                                         const Fr* __restrict__ coef, uint32_t n_entries, const Fr* __restrict__ side,
+                                                         const Fr* __restrict__ rows, uint32_t M,
+                                                         const unsigned long long* __restrict__ verdict,
+                                                         const unsigned long long* __restrict__ known, const uint32_t* __restrict__ cnt,
+                                                         const uint32_t* __restrict__ xr, uint32_t n_wires, uint32_t* by,
+                                                         uint32_t* __restrict__ front, DetState* st)
+{
+    const uint32_t k   = blockIdx.x * blockDim.x + threadIdx.x;
+    bool           add = false;
+    uint32_t       x   = 0;
+    if (k < n) {
+        const uint32_t c = cand[k];
+        if (c < M && !det_bit(verdict, c) && cnt[c] == 1u) {
+            const uint32_t idx = xr[c];
+            if (idx < n_pairs) {
+                x = wire[idx];
+                if (x < n_wires && !det_bit(known, x)) {
+                    const IncTerms t = inc_terms(inc[idx], coef, n_entries, side, rows, M);
+                    if (fr9_nonzero(t.lin) != t.has_quad) add = atomicMin(&by[x], c) == DET_NONE; // a PIN
+                }
+            }
+        }
+    }
+    wave_append(front, &st->n_front, n_wires, add, x);
+}
+
+// front[from .. st->n_front): the wires this round derived (the size is final: k_r1cs_det_derive has ended); a workgroup strides
+// them, so any grid covers them.  start[i] .. start[i + 1]: the column of wire i in inc.  Launched with whole waves, DET_GRID
+// workgroups at the most (the tickets of det_publish, as in k_r1cs_det_first).
+__global__ void __launch_bounds__(256) k_r1cs_det_expand(const uint32_t* __restrict__ front, uint32_t from, uint32_t round,
+                                                         const uint32_t* __restrict__ start, const uint4* __restrict__ inc,
+                                                         uint32_t n_pairs, uint32_t n_wires, uint32_t M, unsigned long long* known,
+                                                         uint32_t* __restrict__ round_of, uint32_t* cnt, uint32_t* xr,
+                                                         uint32_t* __restrict__ cand, DetState* st, DetRecord* rec)
+{
+    const uint32_t lane  = threadIdx.x & 63u;
+    const uint32_t total = __atomic_load_n(&st->n_front, __ATOMIC_RELAXED);
+    const uint32_t todo  = total > from ? total - from : 0; // (the same in every lane: whole workgroups take the same trips)
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < todo; base += (uint64_t)gridDim.x * 256u) {
+        const uint64_t k = base + threadIdx.x;
+        uint32_t       x = DET_NONE, s = 0, e = 0;
+        if (k < todo) {
+            const uint32_t f = front[from + k];
+            if (f < n_wires) {
+                x           = f;
+                round_of[x] = round;
+                s           = start[x];
+                e           = min(start[x + 1], n_pairs);
+            }
+        }
+        wave_or_into(known, x >> 6, x != DET_NONE ? 1ull << (x & 63u) : 0ull);
+        // one incidence: leaves the outside count of its constraint
+        auto leave = [&](bool act, uint32_t idx) {
+            bool     listed = false;
+            uint32_t c      = 0;
+            if (act) {
+                c = inc[idx].x;
+                if (c < M) {
+                    listed = atomicSub(&cnt[c], 1u) == 2u;
+                    atomicXor(&xr[c], idx);
+                }
+            }
+            wave_append(cand, &st->n_cand, M, listed, c);
+        };
+        const uint32_t len = e > s ? e - s : 0;
+        for (uint32_t j = 0; j < DET_SHORT; j++) {
+            const bool act = len <= DET_SHORT && j < len;
+            if (!__ballot(act)) break;
+            leave(act, s + j);
+        }
+        unsigned long long longs = __ballot(len > DET_SHORT);
+        while (longs) {
+            const int src = __ffsll((long long)longs) - 1;
+            longs &= longs - 1;
+            const uint32_t ls = __shfl(s, src, 64), le = __shfl(e, src, 64);
+            for (uint64_t at = ls; at < le; at += 64u) leave(at + lane < le, (uint32_t)(at + lane));
+        }
+    }
+    det_publish(st, rec);
+}
+
 // What a prove call keeps of its check (pinned, device-mapped; read by the host after the check is joined).
 struct CheckRecord {
     unsigned long long flags;                    // WTNS_* of k_r1cs_wtns
@@ -389,6 +572,15 @@ struct k16_r1cs {
     uint32_t *          d_list = nullptr, *h_list = nullptr;   // [n_wires] the listed wires, device / pinned
     Fr*                 d_shift = nullptr;                     // [n_wires] their shifts, standard form
     bool                second_ready = false;
+    // the determinism closure, on top of the same list: made by its first call, kept until the object goes
+    uint32_t*           d_det_start = nullptr;                     // [n_wires + 1] the columns of the device list
+    unsigned long long *d_det_masks = nullptr, *h_det_masks = nullptr; // seed | known, [ceil(n_wires / 64)] each, device / pinned
+    uint32_t*           d_det_cnt   = nullptr;                     // cnt | xr, [M] each
+    uint32_t*           d_det_by    = nullptr;                     // by | round, [n_wires] each
+    uint32_t *          d_det_cand = nullptr, *d_det_front = nullptr; // [M] / [n_wires]: the two lists
+    DetState*           d_det_state = nullptr;
+    DetRecord *         h_det_rec = nullptr, *d_det_rec = nullptr; // pinned, device-mapped
+    bool                det_ready = false;
 };
 
 void k16_r1cs_view(const k16_r1cs* r, k16_ctx** ctx, const R1csFile** file)
@@ -419,10 +611,23 @@ static void r1cs_second_free(k16_r1cs* r)
     r->second_ready = false;
 }
 
+static void r1cs_det_free(k16_r1cs* r)
+{
+    void* bufs[] = {r->d_det_start, r->d_det_masks, r->d_det_cnt, r->d_det_by, r->d_det_cand, r->d_det_front, r->d_det_state};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (r->h_det_masks) (void)hipHostFree(r->h_det_masks);
+    if (r->h_det_rec) (void)hipHostFree(r->h_det_rec);
+    r->d_det_start = nullptr, r->d_det_masks = nullptr, r->h_det_masks = nullptr, r->d_det_cnt = nullptr, r->d_det_by = nullptr;
+    r->d_det_cand = nullptr, r->d_det_front = nullptr, r->d_det_state = nullptr, r->h_det_rec = nullptr, r->d_det_rec = nullptr;
+    r->det_ready = false;
+}
+
 static void r1cs_free(k16_r1cs* r)
 {
     if (!r) return;
     if (r->ctx) (void)hipSetDevice(r->ctx->device);
+    r1cs_det_free(r);
     r1cs_second_free(r);
     r1cs_scan_free(r);
     void* bufs[] = {r->d_slices, r->d_longs, r->d_rowof, r->d_wire, r->d_coef, r->d_wtns, r->d_n16, r->d_rows, r->d_mask};
@@ -960,6 +1165,184 @@ extern "C" int k16_r1cs_second_values(k16_r1cs* r, uint64_t* n_two_valued, uint3
         *n_two_valued = 0;
         return rc;
     }
+    return K16_OK;
+    });
+}
+
+// ---- the determinism closure
+// column starts, masks, the two words per constraint, the maps and the two lists, by the first call
+static int r1cs_det_alloc(k16_ctx* ctx, k16_r1cs* r)
+{
+    const R1csPairs& P     = *r->pairs;
+    const size_t     words = P.present.size(), n = r->n_wires, M = r->M;
+    int              rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_det_start, (n + 1) * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_det_masks, 2 * words * 8))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_det_cnt, 2 * M * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_det_by, 2 * n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_det_cand, M * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_det_front, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, (void**)&r->d_det_state, sizeof(DetState)))) return rc;
+    K16_HIP(ctx, hipHostMalloc((void**)&r->h_det_masks, std::max<size_t>(2 * words * 8, 8), hipHostMallocDefault));
+    K16_HIP(ctx, hipHostMalloc((void**)&r->h_det_rec, sizeof(DetRecord), hipHostMallocMapped | hipHostMallocCoherent));
+    K16_HIP(ctx, hipHostGetDevicePointer((void**)&r->d_det_rec, r->h_det_rec, 0));
+    // the device list leaves wire 0's column out: its columns start that much lower
+    const uint32_t        skip = P.start[1];
+    std::vector<uint32_t> start(n + 1);
+    for (size_t i = 0; i <= n; i++) start[i] = std::max(P.start[i], skip) - skip;
+    K16_HIP(ctx, hipMemcpyAsync(r->d_det_start, start.data(), (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    K16_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (start is a local)
+    r->det_ready = true;
+    return K16_OK;
+}
+
+// h_det_masks[0 .. words) holds the seed.  Leaves `known` in h_det_masks[words ..) and the maps on the device.
+static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds)
+{
+    const R1csPairs& P     = *r->pairs;
+    const uint32_t   n     = (uint32_t)P.pair.size() - P.start[1]; // all but wire 0's column
+    const size_t     words = P.present.size();
+    const uint32_t   M = r->M, n_wires = r->n_wires;
+    hipStream_t      st = ctx->stream;
+    unsigned long long *d_seed = r->d_det_masks, *d_known = r->d_det_masks + words;
+    uint32_t *          d_cnt = r->d_det_cnt, *d_xr = r->d_det_cnt + M, *d_by = r->d_det_by, *d_round = r->d_det_by + n_wires;
+    auto blocks = [](uint64_t lanes) { return dim3((unsigned)((lanes + 255) / 256)); };
+    auto capped = [](uint64_t lanes) { return dim3((unsigned)std::min<uint64_t>((lanes + 255) / 256, DET_GRID)); };
+    *n_rounds   = 0;
+    r->h_det_rec->n_front = r->h_det_rec->n_cand = 0;
+    K16_HIP(ctx, hipMemcpyAsync(d_seed, r->h_det_masks, words * 8, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_known, r->h_det_masks, words * 8, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemsetAsync(r->d_det_by, 0xff, 2 * (size_t)n_wires * 4, st));
+    K16_HIP(ctx, hipMemsetAsync(r->d_det_state, 0, sizeof(DetState), st));
+    if (n && M) {
+        K16_HIP(ctx, hipMemsetAsync(r->d_det_cnt, 0, 2 * (size_t)M * 4, st));
+        {
+            k16_stat_scope sc(ctx, "r1cs_det_init", st);
+            hipLaunchKernelGGL(k_r1cs_det_init, blocks(n), dim3(256), 0, st, r->d_inc, r->d_incwire, n, n_wires, M, d_seed, d_cnt, d_xr);
+            hipLaunchKernelGGL(k_r1cs_det_first, capped(M), dim3(256), 0, st, d_cnt, M, r->d_det_cand, r->d_det_state, r->d_det_rec);
+        }
+        K16_HIP(ctx, hipGetLastError());
+    }
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    // round k judges the candidates [c0, c1) and derives the frontier [f0, f1)
+    uint32_t c0 = 0, c1 = r->h_det_rec->n_cand, f0 = 0, round = 0;
+    while (c1 > c0) {
+        // every round that goes on adds a wire, and wire 0 is never added: at most n_wires - 1 rounds
+        if (round + 1 >= n_wires || c1 > M) {
+            ctx->err = "determinism closure: more rounds than wires";
+            return K16_ERR_HIP;
+        }
+        round++;
+        {
+            k16_stat_scope sc(ctx, "r1cs_det_derive", st);
+            hipLaunchKernelGGL(k_r1cs_det_derive, blocks(c1 - c0), dim3(256), 0, st, r->d_det_cand + c0, c1 - c0, r->d_inc,
+                               r->d_incwire, n, r->d_coef, P.n_entries, r->d_side, r->d_rows, M, r->d_mask, d_known, d_cnt, d_xr,
+                               n_wires, d_by, r->d_det_front, r->d_det_state);
+        }
+        {
+            // a candidate derives one wire at the most: the frontier is no longer than the candidates' range
+            k16_stat_scope sc(ctx, "r1cs_det_expand", st);
+            hipLaunchKernelGGL(k_r1cs_det_expand, capped(c1 - c0), dim3(256), 0, st, r->d_det_front, f0, round, r->d_det_start,
+                               r->d_inc, n, n_wires, M, d_known, d_round, d_cnt, d_xr, r->d_det_cand, r->d_det_state, r->d_det_rec);
+        }
+        K16_HIP(ctx, hipGetLastError());
+        K16_HIP(ctx, hipStreamSynchronize(st));
+        const uint32_t f1 = r->h_det_rec->n_front, c2 = r->h_det_rec->n_cand;
+        if (f1 < f0 || f1 > n_wires || c2 < c1) {
+            ctx->err = "determinism closure: a list shrank or outgrew its room";
+            return K16_ERR_HIP;
+        }
+        if (f1 == f0) { // nothing derived: the level before was the fixed point
+            round--;
+            break;
+        }
+        f0 = f1, c0 = c1, c1 = c2;
+    }
+    *n_rounds = round;
+    K16_HIP(ctx, hipMemcpyAsync(r->h_det_masks + words, d_known, words * 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+// round and by as the device left them (the caller writes round 0 for the seed), only when asked for
+static int r1cs_det_maps(k16_ctx* ctx, k16_r1cs* r, uint32_t* h_round, uint32_t* h_by)
+{
+    const size_t bytes = (size_t)r->n_wires * 4;
+    if (h_by) K16_HIP(ctx, hipMemcpyAsync(h_by, r->d_det_by, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_round) K16_HIP(ctx, hipMemcpyAsync(h_round, r->d_det_by + r->n_wires, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    K16_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_determined_wires(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_seed, uint64_t* n_derived, uint64_t* n_absent,
+                                         uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
+                                         uint32_t* h_round, uint32_t* h_by)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_derived || !n_absent || !n_open || !n_rounds || (!h_seed && n_seed)) return K16_ERR_ARG;
+    *n_derived = *n_absent = *n_open = 0;
+    *n_rounds                        = 0;
+    k16_ctx* ctx                     = r->ctx;
+    if (!r->have_values || r->forked_on) {
+        ctx->err = "no completed check to scan";
+        return K16_ERR_ARG;
+    }
+    // the default seed: what the file's header calls inputs, in the iden3 wire order 1 | public outputs | public inputs | private inputs
+    const uint64_t in0 = (uint64_t)r->file.n_pub_out + 1, in1 = in0 + r->file.n_pub_in + r->file.n_prv_in;
+    if (!h_seed && in1 > r->n_wires) {
+        ctx->err = "the header's input wires reach beyond nWires";
+        return K16_ERR_ARG;
+    }
+    for (uint32_t k = 0; k < n_seed; k++)
+        if (h_seed[k] >= r->n_wires) {
+            ctx->err = "seed wire number out of range";
+            return K16_ERR_ARG;
+        }
+    int rc = r1cs_pairs_get(ctx, r);
+    if (rc) return rc;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    if (!r->scan_ready) rc = r1cs_scan_upload(ctx, r);
+    if (!rc && !r->det_ready) rc = r1cs_det_alloc(ctx, r);
+    const size_t        words = r->pairs->present.size();
+    unsigned long long* seed  = r->h_det_masks;
+    if (!rc) {
+        memset(seed, 0, words * 8);
+        seed[0] = 1ull; // wire 0
+        if (h_seed)
+            for (uint32_t k = 0; k < n_seed; k++) seed[h_seed[k] >> 6] |= 1ull << (h_seed[k] & 63u);
+        else
+            for (uint64_t i = in0; i < in1; i++) seed[i >> 6] |= 1ull << (i & 63u);
+        rc = r1cs_det_run(ctx, r, n_rounds);
+    }
+    if (!rc && (h_round || h_by)) rc = r1cs_det_maps(ctx, r, h_round, h_by);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream); // nothing of the scan stays in flight
+        if (!r->det_ready) r1cs_det_free(r);
+        if (!r->scan_ready) r1cs_scan_free(r);
+        *n_rounds = 0;
+        return rc;
+    }
+    const R1csPairs&          P     = *r->pairs;
+    const unsigned long long* known = r->h_det_masks + words;
+    uint64_t                  derived = 0, absent = 0, open = 0, listed = 0;
+    for (size_t w = 0; w < words; w++) {
+        const uint32_t           in_word = (uint32_t)std::min<uint64_t>(64, (uint64_t)r->n_wires - 64 * (uint64_t)w);
+        const unsigned long long valid = in_word == 64 ? ~0ull : (1ull << in_word) - 1, here = P.present[w];
+        const unsigned long long out = ~known[w] & valid, got = known[w] & ~seed[w] & valid;
+        derived += (uint64_t)__builtin_popcountll(got);
+        absent += (uint64_t)__builtin_popcountll(out & ~here);
+        open += (uint64_t)__builtin_popcountll(out & here);
+        if (h_status)
+            for (uint32_t b = 0; b < in_word; b++)
+                h_status[64 * w + b] = (seed[w] >> b) & 1   ? K16_DET_SEED
+                                       : (got >> b) & 1     ? K16_DET_DERIVED
+                                       : (here >> b) & 1    ? K16_DET_OPEN
+                                                            : K16_DET_ABSENT;
+        if (h_round)
+            for (unsigned long long m = seed[w] & valid; m; m &= m - 1) h_round[64 * w + (uint32_t)__builtin_ctzll(m)] = 0;
+        for (unsigned long long m = out & here; m && listed < cap && h_wires; m &= m - 1) h_wires[listed++] = (uint32_t)(64 * w + (uint32_t)__builtin_ctzll(m));
+    }
+    *n_derived = derived, *n_absent = absent, *n_open = open;
     return K16_OK;
     });
 }

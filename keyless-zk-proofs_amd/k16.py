@@ -49,6 +49,7 @@ SYMBOLS = [
     "k16_r1cs_create", "k16_r1cs_create_mem", "k16_r1cs_destroy", "k16_r1cs_info", "k16_r1cs_check_mem", "k16_r1cs_check_file",
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
     "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences", "k16_r1cs_second_values",
+    "k16_r1cs_determined_wires",
     "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
@@ -178,6 +179,8 @@ def load():
     L.k16_r1cs_wire_constraints.argtypes = [vp, u32, C.POINTER(u64), vp, u32]
     L.k16_r1cs_incidences.argtypes = [vp, C.POINTER(u64)]
     L.k16_r1cs_second_values.argtypes = [vp, C.POINTER(u64), vp, vp, u32, vp]
+    L.k16_r1cs_determined_wires.argtypes = [vp, vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), vp, u32,
+                                            vp, vp, vp]
     L.k16_prover_set_r1cs.argtypes = [vp, vp]
     L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
     L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
@@ -530,6 +533,8 @@ def points_sum(group, parts):
 R1CS_REPORT_MAX = 64
 CHECK_NONE, CHECK_SATISFIED, CHECK_BROKEN, CHECK_WITNESS_REFUSED = 0, 1, 2, 3
 WIRE_BOUND, WIRE_ABSENT, WIRE_UNBOUND, WIRE_TWO_VALUED = 0, 1, 2, 3
+DET_SEED, DET_DERIVED, DET_ABSENT, DET_OPEN = 0, 1, 2, 3
+DET_NONE = 0xFFFFFFFF
 
 
 def fullprover_set_r1cs(fullprover, r1cs_path):
@@ -769,6 +774,30 @@ class R1cs:
         k = min(int(n.value), cap)
         out = (int(n.value), wires[:k].copy(), [int.from_bytes(shifts[i].tobytes(), "little") for i in range(k)])
         return out + (full,) if status else out
+
+    def determined_wires(self, seed=None, cap=None, want_maps=False):
+        """k16_r1cs_determined_wires on the sums of the last completed check: (n_derived, n_absent, n_open, n_rounds, wires) with
+        the lowest min(n_open, cap) DET_OPEN wires, ascending; cap=None asks for all of them.  seed: the wires whose values are
+        given (wire 0 is added); None: the inputs the .r1cs header names.  want_maps=True appends the class of every wire
+        (uint8), its round and its deriving constraint (uint32, DET_NONE where there is none)."""
+        n_wires = self.info()["n_wires"]
+        cap = n_wires if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("cap must not be negative")
+        if seed is not None:
+            seed = [int(s) for s in seed]
+            if any(s < 0 or s > 0xFFFFFFFF for s in seed):
+                raise ValueError("a seed wire is no 32-bit number")
+            n_seed, seed = len(seed), np.array(seed or [0], dtype=np.uint32)     # (an empty list is no NULL)
+        wires = np.zeros(max(cap, 1), dtype=np.uint32)
+        status = np.zeros(n_wires, dtype=np.uint8) if want_maps else None
+        rounds, by = (np.zeros(n_wires, dtype=np.uint32) for _ in range(2)) if want_maps else (None, None)
+        nd, na, no, nr = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self.ctx._chk(self.ctx.L.k16_r1cs_determined_wires(
+            self.h, _p(seed) if seed is not None else None, 0 if seed is None else n_seed, C.byref(nd), C.byref(na),
+            C.byref(no), C.byref(nr), _p(wires), cap, *((_p(status), _p(rounds), _p(by)) if want_maps else (None, None, None))))
+        out = (int(nd.value), int(na.value), int(no.value), int(nr.value), wires[:min(int(no.value), cap)].copy())
+        return out + (status, rounds, by) if want_maps else out
 
     def wire_constraints(self, wire, cap=None):
         """k16_r1cs_wire_constraints: (n, ndarray of the lowest min(n, cap) constraints the wire has a non-zero merged
