@@ -739,5 +739,11 @@ K16_HD Fr fr9_to_standard(const Fr9& a)
     cond_sub_p<FrParams>(r.v);
     return r;
 }
+// x != 0 (mod r)?  x is a lazy representative below 2r: only the canonical form tells r from 0
+K16_HD bool fr9_nonzero(const Fr9& x)
+{
+    const Fr d = fr9_to_standard(x);
+    return (d.v[0] | d.v[1] | d.v[2] | d.v[3] | d.v[4] | d.v[5] | d.v[6] | d.v[7]) != 0;
+}
 
 } // namespace k16

@@ -1,0 +1,776 @@
+// r1cs_scan.hip -- the diagnostics on top of the R1CS witness check (include/k16.h; r1cs_check.hip makes what they read): three
+// questions about the sums a completed check left in d_rows, all answered by walks over ONE list, the (wire, constraint)
+// incidences of the circuit (r1cs_pairs.h), ordered by wire.
+//   k16_r1cs_unbound_wires     which wires could take any value without moving a residual?  k_r1cs_incidences
+//   k16_r1cs_second_values     which admit exactly ONE other value, every other wire held fixed?  k_r1cs_kinds, _agree, _shifts (10c)
+//   k16_r1cs_determined_wires  which does the circuit force, given the seed wires?  k_r1cs_det_init, _first, _derive, _expand (10d)
+// Each kernel is described where it stands.  The list and every buffer here are made by the first call that needs them: create
+// and check calls allocate and launch nothing of this file.  From masks to counts, lists and status bytes: r1cs_masks.h.
+#include <string.h>
+#include <memory>
+#include <string>
+#include <vector>
+#include "r1cs_obj.h"
+#include "frinv_dev.h"
+#include "r1cs_masks.h"
+#include "r1cs_pairs.h"
+#include "spmv_dev.h"
+
+using namespace k16;
+
+static_assert(sizeof(R1csPair) == sizeof(uint4), "an incidence is one 16-byte load");
+
+namespace {
+
+// The runs of neighbouring lanes of a wave that hold the same key (here: the same mask word, or the same wire -- the list is
+// ordered by wire).  first: the first lane of my run, last: I am its last lane.  Needs the whole wave.
+struct WaveRun {
+    uint32_t           first;
+    bool               last;
+    unsigned long long below; // the lanes of my run before me
+};
+__device__ __forceinline__ WaveRun wave_run(uint32_t key)
+{
+    const uint32_t           lane  = threadIdx.x & 63u;
+    const uint32_t           prev  = __shfl_up(key, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || key != prev);               // first lane of each run (bit 0 is set)
+    const unsigned long long upto  = lane == 63u ? ~0ull : (1ull << (lane + 1)) - 1;   // lanes 0 .. lane
+    WaveRun                  r;
+    r.first = 63u - (uint32_t)__clzll((long long)(heads & upto));
+    r.last  = lane == 63u || ((heads >> (lane + 1)) & 1ull) != 0;
+    r.below = (upto >> 1) & ~((1ull << r.first) - 1);
+    return r;
+}
+// mask[word] |= the OR of `bits` over each run of lanes that share `word` (a segmented inclusive scan upwards; the run's last lane
+// stores).  The mask was cleared before the launch and bits are only ever set: a read that lags behind can only miss bits that
+// are set by now -- the atomic is then issued for nothing, the mask is the same.  Other lanes update the word atomically, so the
+// read is a relaxed atomic load and `mask` is no __restrict__ pointer: the compiler may not hoist or merge it.
+__device__ __forceinline__ void wave_or_into(unsigned long long* mask, uint32_t word, unsigned long long bits)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const WaveRun  run  = wave_run(word);
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const unsigned long long up = __shfl_up(bits, d, 64);
+        if (lane >= run.first + d) bits |= up;
+    }
+    if (run.last && bits && (__atomic_load_n(&mask[word], __ATOMIC_RELAXED) & bits) != bits) atomicOr(&mask[word], bits);
+}
+
+// The terms of an incidence.  Change wire i alone by d: the residual a_c b_c - c_c of constraint c moves by d lin + d^2 quad with
+//   lin = A^ b_c + B^ a_c - C^,  quad = A^ B^      (A^, B^, C^: the merged coefficients of wire i in constraint c)
+// quad: r is prime, so a product of two non-zero residues is non-zero, and r1cs_pairs.h names a coefficient only when its merged
+// sum is non-zero: quad != 0 exactly when the incidence names both A^ and B^.  Whether it is zero needs no product.
+// Scalings: a coefficient k is stored as k * 2^522 mod r (coef, and side in the same scaling), a sum s lies in rows as the R'
+// value s * 2^261; frmul9 divides by 2^261.  Bounds: coefficients < r, sums < 2r (+ 2^-17 r): every product below is < 2r.
+//   lin   frmul9(A^ 2^522, b 2^261) + frmul9(B^ 2^522, a 2^261) - C^ 2^522  =  lin 2^522: the products and the bare C^ term carry
+//         the SAME factor.  Where one of A^, B^ is absent, lin is ONE product (or none) minus C^; where both are there, fradd9 of
+//         two values < 2r (its bound is < 4r); then frsub9 with the subtrahend C^ 2^522 < r (its bound is < 2r).  fr9_nonzero
+//         divides by 2^261 once more and looks at the canonical representative of lin * 2^261: zero exactly when r divides lin
+//         (the operands are lazy representatives below 2r, as in k_r1cs_judge)
+//   quad  frmul9(A^ 2^522, B^ 2^522) = quad 2^783; coefficients < r: the product is < 2r.  The kind of an incidence does not
+//         need it, the comparison and the shift do
+//   two ROOTs (lin, quad), (lin0, quad0) give the same d exactly when lin quad0 = lin0 quad (quad, quad0 != 0):
+//         frmul9(lin 2^522, quad0 2^783) and frmul9(lin0 2^522, quad 2^783) both carry 2^1044; operands < 2r, products < 2r, and
+//         the difference goes through fr9_nonzero: products of coefficients like r - 1 agree only modulo r
+//   d     frmul9(quad 2^783, 1) = quad 2^522 = (quad 2^261) 2^261, the R' value of quad 2^261; frinv9 returns the R' value of
+//         its inverse, quad^-1 2^-261 2^261 = quad^-1 with factor 1; frmul9(lin 2^522, quad^-1) = (lin / quad) 2^261, an R' value
+//         again, negated by frsub9(0, .) -- and fr9_to_standard divides by 2^261: the canonical -lin / quad.
+//
+// The device list as every kernel sees it, one kernel argument.  inc / wire: n_pairs incidences ordered by wire and, within a
+// wire, by constraint (the host leaves wire 0's column out, see k_r1cs_incidences); inc[i].x: the constraint, .y / .z / .w: the
+// positions of A^ / B^ / C^.  Positions: < n_entries -> coef, n_entries + k -> side[k], R1CS_PAIR_NONE -> 0.  rows: A.w | B.w |
+// C.w of the last completed check, M packed R' values each.
+struct IncList {
+    const uint4* __restrict__ inc;
+    const uint32_t* __restrict__ wire;
+    uint32_t n_pairs;
+    const Fr* __restrict__ coef;
+    uint32_t n_entries;
+    const Fr* __restrict__ side;
+    const Fr* __restrict__ rows;
+    uint32_t M;
+    __device__ __forceinline__ Fr9 at(uint32_t p) const { return ld_r9(p < n_entries ? &coef[p] : &side[p - n_entries]); }
+};
+struct IncTerms {
+    Fr9  lin;
+    bool has_quad; // both A^ and B^ are there: quad != 0
+};
+// lin 2^522 of incidence e
+__device__ __forceinline__ IncTerms inc_terms(const uint4 e, const IncList& L)
+{
+    const bool a = e.y != R1CS_PAIR_NONE, b = e.z != R1CS_PAIR_NONE;
+    IncTerms   t;
+    t.lin      = fq9_zero();
+    t.has_quad = a && b;
+    if (a || b) { // B^ a_c where B^ is there, else A^ b_c: the one product, or the second of two
+        t.lin = frmul9(L.at(b ? e.z : e.y), ld_r9(&L.rows[b ? e.x : (size_t)L.M + e.x]));
+        if (t.has_quad) t.lin = fradd9(frmul9(L.at(e.y), ld_r9(&L.rows[(size_t)L.M + e.x])), t.lin);
+    }
+    if (e.w != R1CS_PAIR_NONE) t.lin = frsub9(t.lin, L.at(e.w));
+    return t;
+}
+// quad 2^783 of an incidence that names both
+__device__ __forceinline__ Fr9 inc_quad(const uint4 e, const IncList& L) { return frmul9(L.at(e.y), L.at(e.z)); }
+
+// The unbound-wire scan: a wire is bound by constraint c when lin != 0 or quad != 0 (mod r).  An incidence that names both A^
+// and B^ is bound without any product.
+// bound: ceil(n_wires / 64) words, cleared before the launch, bit i = wire i is bound.  The list is ordered by wire, so the
+// lanes of a wave whose wires share a mask word are neighbours: their bits are ORed over the wave first and ONE lane per word
+// issues the atomicOr, and only where the word does not show the bits yet (atomics on ONE address queue up behind each other
+// across the whole device: a wire that sits in a large part of the constraints would cost one per wave); an OR gives the same
+// mask whatever order the lanes run in.  Wire 0, the constant, is BOUND by definition: the host leaves its column -- the
+// longest of a real circuit -- out of the launch.  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_incidences(const IncList L, unsigned long long* bound)
+{
+    const uint32_t i   = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t       w   = 0xffffffffu; // (no wire: the lanes behind the list)
+    bool           hit = false;
+    if (i < L.n_pairs) {
+        const uint4 e = L.inc[i];
+        w             = L.wire[i];
+        hit           = (e.y != R1CS_PAIR_NONE && e.z != R1CS_PAIR_NONE) || fr9_nonzero(inc_terms(e, L).lin);
+    }
+    wave_or_into(bound, w >> 6, hit ? 1ull << (w & 63u) : 0ull);
+}
+
+// The second-value scan.  An incidence is FREE (lin = quad = 0: every d leaves the residual), a PIN
+// (exactly one of them is zero: no d != 0 leaves it -- d lin = 0 or d^2 quad = 0 has the root 0 alone, r being prime) or a ROOT
+// (neither is zero: d lin + d^2 quad = 0 has exactly one other root, d = -lin / quad).  A wire is TWO-VALUED when it has no PIN,
+// at least one ROOT, and all its ROOTs give the same d.
+// pinned / rooted: ceil(n_wires / 64) words each, cleared before the launch: bit i = wire i has a PIN / a ROOT incidence,
+// merged per word and wave as in k_r1cs_incidences.  ref[n_wires], all ones before the launch: the lowest ROOT incidence of each
+// wire.  The list is ordered by wire and, within a wire, ascending: among the lanes of a wave that share a wire the FIRST ROOT
+// lane holds the wave's minimum, it alone issues the atomicMin, and only where ref does not show an index that low yet (ref only
+// ever falls: a read that lags behind costs an atomic for nothing).  One atomic per wire and wave at the most, however long the
+// column; a minimum is the same whatever order the lanes run in.  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_kinds(const IncList L, unsigned long long* pinned, unsigned long long* rooted, uint32_t* ref)
+{
+    const uint32_t i   = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t       w   = 0xffffffffu; // (no wire: the lanes behind the list)
+    bool           pin = false, root = false;
+    if (i < L.n_pairs) {
+        w                 = L.wire[i];
+        const IncTerms t  = inc_terms(L.inc[i], L);
+        const bool     nz = fr9_nonzero(t.lin);
+        pin               = nz != t.has_quad;
+        root              = nz && t.has_quad;
+    }
+    const unsigned long long bit = 1ull << (w & 63u);
+    wave_or_into(pinned, w >> 6, pin ? bit : 0ull);
+    wave_or_into(rooted, w >> 6, root ? bit : 0ull);
+    const WaveRun            run   = wave_run(w);
+    const unsigned long long roots = __ballot(root);
+    if (root && (roots & run.below) == 0 && __atomic_load_n(&ref[w], __ATOMIC_RELAXED) > i) atomicMin(&ref[w], i);
+}
+
+// A ROOT incidence other than its wire's reference: lin quad0 = lin0 quad?  Where not, the two move the wire to different
+// values and the wire's bit is set in `pinned` (no single d != 0 serves both).  Equality with ONE reference is equality of all
+// the d of a wire, since every quad is non-zero.  Nothing per incidence is kept between the kernels: the reference's terms are
+// formed again, two products.  Launched with whole waves, after k_r1cs_kinds on the same stream.
+__global__ void __launch_bounds__(256) k_r1cs_agree(const IncList L, const uint32_t* __restrict__ ref, unsigned long long* pinned)
+{
+    const uint32_t i     = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t       w     = 0xffffffffu;
+    bool           clash = false;
+    if (i < L.n_pairs) {
+        w             = L.wire[i];
+        const uint4 e = L.inc[i];
+        const uint32_t j = ref[w];
+        if (e.y != R1CS_PAIR_NONE && e.z != R1CS_PAIR_NONE && j != i && j < L.n_pairs) {
+            const IncTerms t = inc_terms(e, L);
+            if (fr9_nonzero(t.lin)) {
+                const uint4    e0 = L.inc[j];
+                const IncTerms t0 = inc_terms(e0, L);
+                clash = fr9_nonzero(frsub9(frmul9(t.lin, inc_quad(e0, L)), frmul9(t0.lin, inc_quad(e, L))));
+            }
+        }
+    }
+    wave_or_into(pinned, w >> 6, clash ? 1ull << (w & 63u) : 0ull);
+}
+
+// list[n]: two-valued wires; shift[k] = -lin0 / quad0 of list[k]'s reference incidence, standard form (canonical; non-zero, as
+// lin0 != 0).  One inversion per lane: the work is the list's, not the circuit's.
+__global__ void __launch_bounds__(64) k_r1cs_shifts(const uint32_t* __restrict__ list, uint32_t n, const IncList L,
+                                                    const uint32_t* __restrict__ ref, Fr* __restrict__ shift)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t j = ref[list[k]];
+    if (j >= L.n_pairs) return; // (a listed wire has a ROOT incidence)
+    const uint4    e0 = L.inc[j];
+    const IncTerms t0 = inc_terms(e0, L);
+    Fr9            one = fq9_zero();
+    one.l[0]           = 1;
+    const Fr9 qinv = frinv9(frmul9(inc_quad(e0, L), one));
+    st_fr(&shift[k], fr9_to_standard(frsub9(fq9_zero(), frmul9(t0.lin, qinv))));
+}
+
+// The determinism closure (k16_r1cs_determined_wires): the least set K of wires that holds the seed and
+// is closed under
+//     constraint c is not broken, exactly ONE wire x with a non-zero merged coefficient in c lies outside K, and the
+//     incidence (x, c) is a PIN  ==>  x joins K
+// computed level by level (K_0 = seed, K_k+1 = K_k and what the rule gives with respect to K_k): round[x] is the first level
+// that holds x, by[x] the lowest constraint that gave it there.  Any witness that satisfies the circuit and agrees with this one
+// on the seed agrees with it on K: in c every wire but x is equal, so the residuals differ by t lin + t^2 quad, both residuals
+// are 0, and a PIN leaves t = 0 alone.  Three details of the rule carry that argument -- none of them is an inefficiency:
+//   a BROKEN constraint derives nothing     its residual under this witness is not 0, the difference says nothing about t
+//   a FREE incidence of an outside wire still COUNTS as an outside wire     two outside wires x, y move the residual by a cross
+//                                           term dx dy (A^x B^y + A^y B^x) that neither wire's lin or quad shows
+//   a ROOT derives nothing                  t = -lin / quad is the second solution: the two-valued case
+// Each constraint carries two words: cnt[c], the number of its incidences (of the device list: wire 0, always in K, is not on
+// it) whose wire lies outside K, and xr[c], the XOR of those incidences' indices -- where cnt is 1, xr IS the one outside
+// incidence.  No constraint-ordered copy of the list is needed.
+//   k_r1cs_det_init    one lane per incidence: a wire outside the seed counts into cnt / xr of its constraint
+//   k_r1cs_det_first   one lane per constraint: cnt = 1 -> the candidate list
+//   k_r1cs_det_derive  one lane per candidate of this round: not broken, cnt still 1 (a constraint may have fallen on to 0 in
+//                      the expansion that listed it), the outside incidence a PIN -> atomicMin(by[x], c); the lane that found
+//                      by[x] empty appends x to the frontier.  `known` is only read here, so by[x] ends as the minimum over
+//                      exactly the constraints that qualify with respect to the level before
+//   k_r1cs_det_expand  one lane per frontier wire: known bit, round[x], and for each incidence of its column cnt[c] -= 1,
+//                      xr[c] ^= index; the lane that saw cnt fall from 2 to 1 appends c to the candidates -- once per
+//                      constraint, cnt only ever falls.  A column of up to DET_SHORT incidences is walked by its lane, a longer
+//                      one by the whole wave, 64 incidences a step: no lane's work grows with a column's length.
+// Both lists only grow: every constraint becomes a candidate at most once and is judged once (its kind depends on the witness
+// alone: a candidate that is no PIN now never is), every wire enters the frontier at most once; a round is a range of each.  The
+// host reads both list sizes once per round from a record in pinned, device-mapped memory, written by the last workgroup of
+// k_r1cs_det_first / _expand to finish (a ticket per workgroup; nothing waits).  Appends are one atomicAdd per wave and list.
+// The order inside a list is arbitrary and nothing observable depends on it: masks are ORs, by is a minimum, round has one value
+// per wire, cnt is a sum and xr an XOR, the sizes are sums.
+constexpr uint32_t DET_NONE  = 0xffffffffu;
+constexpr uint32_t DET_SHORT = 8;
+constexpr uint32_t DET_GRID  = 512; // workgroups of a kernel that ends in det_publish
+struct DetState {
+    uint32_t n_front, n_cand; // sizes of the two lists
+    uint32_t done, pad;       // workgroups of the running kernel that have finished
+};
+struct DetRecord {
+    uint32_t n_front, n_cand;
+};
+
+// list[*total ...] <- value of the lanes that `have` one: one atomicAdd per wave.  Needs the whole wave.  cap: the list's room
+// (every constraint / wire is appended once at the most, so it is never reached).
+__device__ __forceinline__ void wave_append(uint32_t* __restrict__ list, uint32_t* total, uint32_t cap, bool have, uint32_t value)
+{
+    const unsigned long long votes = __ballot(have);
+    if (!votes) return;
+    const uint32_t lane   = threadIdx.x & 63u;
+    const int      leader = __ffsll((long long)votes) - 1;
+    uint32_t       base   = 0;
+    if ((int)lane == leader) base = atomicAdd(total, (uint32_t)__popcll(votes));
+    base               = __shfl(base, leader, 64);
+    const uint32_t pos = base + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
+    if (have && pos < cap) list[pos] = value;
+}
+// The last workgroup to get here copies the list sizes into the host's record.  Every lane of the workgroup calls it, after its
+// last append.
+__device__ __forceinline__ void det_publish(DetState* st, DetRecord* rec)
+{
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    __threadfence(); // this workgroup's appends before its ticket
+    if (atomicAdd(&st->done, 1u) != gridDim.x - 1) return;
+    __threadfence(); // every other workgroup's ticket before the reads
+    rec->n_front = __atomic_load_n(&st->n_front, __ATOMIC_RELAXED);
+    rec->n_cand  = __atomic_load_n(&st->n_cand, __ATOMIC_RELAXED);
+    st->done     = 0; // (the next launch on the stream starts behind this kernel)
+}
+__device__ __forceinline__ bool det_bit(const unsigned long long* __restrict__ mask, uint32_t i) { return (mask[i >> 6] >> (i & 63u)) & 1ull; }
+
+// cnt / xr: M words each, cleared before the launch.  seed: ceil(n_wires / 64) words.
+__global__ void __launch_bounds__(256) k_r1cs_det_init(const IncList L, uint32_t n_wires, const unsigned long long* __restrict__ seed,
+                                                       uint32_t* cnt, uint32_t* xr)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= L.n_pairs) return;
+    const uint32_t w = L.wire[i], c = L.inc[i].x;
+    if (w >= n_wires || c >= L.M || det_bit(seed, w)) return;
+    atomicAdd(&cnt[c], 1u);
+    atomicXor(&xr[c], i);
+}
+
+// Launched with whole waves, DET_GRID workgroups at the most: a workgroup strides the constraints (every workgroup draws a ticket
+// in det_publish, on ONE counter: a ticket per 256 constraints would cost more than the pass).
+__global__ void __launch_bounds__(256) k_r1cs_det_first(const uint32_t* __restrict__ cnt, uint32_t M, uint32_t* __restrict__ cand,
+                                                        DetState* st, DetRecord* rec)
+{
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < M; base += (uint64_t)gridDim.x * 256u) { // (the same trips for a whole workgroup)
+        const uint64_t c = base + threadIdx.x;
+        wave_append(cand, &st->n_cand, M, c < M && cnt[c] == 1u, (uint32_t)c);
+    }
+    det_publish(st, rec);
+}
+
+// cand[0 .. n): the candidates of this round.  verdict: the check's mask (bit c: constraint c is broken).  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_det_derive(const uint32_t* __restrict__ cand, uint32_t n, const IncList L,
+                                                         const unsigned long long* __restrict__ verdict, const unsigned long long* __restrict__ known,
+                                                         const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ xr, uint32_t n_wires, uint32_t* by,
+                                                         uint32_t* __restrict__ front, DetState* st)
+{
+    const uint32_t k   = blockIdx.x * blockDim.x + threadIdx.x;
+    bool           add = false;
+    uint32_t       x   = 0;
+    if (k < n) {
+        const uint32_t c = cand[k];
+        if (c < L.M && !det_bit(verdict, c) && cnt[c] == 1u) {
+            const uint32_t idx = xr[c];
+            if (idx < L.n_pairs) {
+                x = L.wire[idx];
+                if (x < n_wires && !det_bit(known, x)) {
+                    const IncTerms t = inc_terms(L.inc[idx], L);
+                    if (fr9_nonzero(t.lin) != t.has_quad) add = atomicMin(&by[x], c) == DET_NONE; // a PIN
+                }
+            }
+        }
+    }
+    wave_append(front, &st->n_front, n_wires, add, x);
+}
+
+// front[from .. st->n_front): the wires this round derived (the size is final: k_r1cs_det_derive has ended); a workgroup strides
+// them, so any grid covers them.  start[i] .. start[i + 1]: the column of wire i in inc.  Launched with whole waves, DET_GRID
+// workgroups at the most (the tickets of det_publish, as in k_r1cs_det_first).
+__global__ void __launch_bounds__(256) k_r1cs_det_expand(const uint32_t* __restrict__ front, uint32_t from, uint32_t round,
+                                                         const uint32_t* __restrict__ start, const IncList L, uint32_t n_wires,
+                                                         unsigned long long* known, uint32_t* __restrict__ round_of, uint32_t* cnt, uint32_t* xr,
+                                                         uint32_t* __restrict__ cand, DetState* st, DetRecord* rec)
+{
+    const uint32_t lane  = threadIdx.x & 63u;
+    const uint32_t total = __atomic_load_n(&st->n_front, __ATOMIC_RELAXED);
+    const uint32_t todo  = total > from ? total - from : 0; // (the same in every lane: whole workgroups take the same trips)
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < todo; base += (uint64_t)gridDim.x * 256u) {
+        const uint64_t k = base + threadIdx.x;
+        uint32_t       x = DET_NONE, s = 0, e = 0;
+        if (k < todo) {
+            const uint32_t f = front[from + k];
+            if (f < n_wires) {
+                x           = f;
+                round_of[x] = round;
+                s           = start[x];
+                e           = min(start[x + 1], L.n_pairs);
+            }
+        }
+        wave_or_into(known, x >> 6, x != DET_NONE ? 1ull << (x & 63u) : 0ull);
+        // one incidence: leaves the outside count of its constraint
+        auto leave = [&](bool act, uint32_t idx) {
+            bool     listed = false;
+            uint32_t c      = 0;
+            if (act) {
+                c = L.inc[idx].x;
+                if (c < L.M) {
+                    listed = atomicSub(&cnt[c], 1u) == 2u;
+                    atomicXor(&xr[c], idx);
+                }
+            }
+            wave_append(cand, &st->n_cand, L.M, listed, c);
+        };
+        const uint32_t len = e > s ? e - s : 0;
+        for (uint32_t j = 0; j < DET_SHORT; j++) {
+            const bool act = len <= DET_SHORT && j < len;
+            if (!__ballot(act)) break;
+            leave(act, s + j);
+        }
+        unsigned long long longs = __ballot(len > DET_SHORT);
+        while (longs) {
+            const int src = __ffsll((long long)longs) - 1;
+            longs &= longs - 1;
+            const uint32_t ls = __shfl(s, src, 64), le = __shfl(e, src, 64);
+            for (uint64_t at = ls; at < le; at += 64u) leave(at + lane < le, (uint32_t)(at + lane));
+        }
+    }
+    det_publish(st, rec);
+}
+
+// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Three stages, each made whole by the first call
+// that needs it and kept until the object goes; a stage is ready when its pointer is set.
+struct ScanList { // the list on the device, and the unbound-wire scan's mask
+    DevBuf<uint4>                 inc;     // R1csPair of every incidence of the wires 1 .. n_wires - 1
+    DevBuf<uint32_t>              wire;    // their wires
+    DevBuf<Fr>                    side;    // merged sums * 2^522 mod r
+    DevBuf<unsigned long long>    d_bound; // [ceil(n_wires / 64)]
+    PinnedBuf<unsigned long long> h_bound;
+};
+struct ScanSecond { // the second-value scan
+    DevBuf<unsigned long long>    d_kinds; // pinned | rooted, [ceil(n_wires / 64)] each
+    PinnedBuf<unsigned long long> h_kinds;
+    DevBuf<uint32_t>              d_ref;   // [n_wires] the lowest ROOT incidence of each wire
+    DevBuf<uint32_t>              d_list;  // [n_wires] the listed wires
+    PinnedBuf<uint32_t>           h_list;
+    DevBuf<Fr>                    d_shift; // [n_wires] their shifts, standard form
+};
+struct ScanDet { // the determinism closure
+    DevBuf<uint32_t>              d_start; // [n_wires + 1] the columns of the device list
+    DevBuf<unsigned long long>    d_masks; // seed | known, [ceil(n_wires / 64)] each
+    PinnedBuf<unsigned long long> h_masks;
+    DevBuf<uint32_t>              d_cnt;   // cnt | xr, [M] each
+    DevBuf<uint32_t>              d_by;    // by | round, [n_wires] each
+    DevBuf<uint32_t>              d_cand, d_front; // [M] / [n_wires]: the two lists
+    DevBuf<DetState>              d_state;
+    PinnedBuf<DetRecord>          rec;     // pinned, device-mapped
+};
+
+} // namespace
+
+struct k16::R1csScans {
+    R1csPairs                   pairs; // the host list: by the first call that needs it
+    std::unique_ptr<ScanList>   list;
+    std::unique_ptr<ScanSecond> second;
+    std::unique_ptr<ScanDet>    det;
+};
+void k16::r1cs_scans_delete(R1csScans* s) { delete s; }
+
+// The incidence list, made once.  K16_ERR_ARG: 2^32 incidences or more.
+static int r1cs_pairs_get(k16_ctx* ctx, k16_r1cs* r)
+{
+    if (r->scans) return K16_OK;
+    R1csPlan plan; // the layout k16_r1cs_create_mem uploaded: r1cs_plan_build is a function of the file alone
+    if (r1cs_plan_build(r->file, &plan)) {
+        ctx->err = "r1cs: too many terms for 32-bit entry offsets";
+        return K16_ERR_ARG;
+    }
+    if (plan.plan.n_entries != r->n_entries) { // positions would point into another layout than d_coef's
+        ctx->err = "r1cs: the rebuilt plan is not the one the coefficients were uploaded by";
+        return K16_ERR_ARG;
+    }
+    std::unique_ptr<R1csScans> s(new R1csScans());
+    if (r1cs_pairs_build(r->file, plan, &s->pairs)) {
+        ctx->err = "r1cs: 2^32 (wire, constraint) incidences or more";
+        return K16_ERR_ARG;
+    }
+    r->scans.reset(s.release());
+    return K16_OK;
+}
+
+// hipMalloc for the scans: out of device memory is K16_ERR_NOMEM
+template <class T>
+static int r1cs_scan_alloc(k16_ctx* ctx, DevBuf<T>& b, size_t bytes)
+{
+    const hipError_t e = b.alloc(std::max<size_t>(bytes, 32));
+    if (e == hipSuccess) return K16_OK;
+    ctx->err = std::string("unbound-wire scan: hipMalloc: ") + hipGetErrorString(e);
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? K16_ERR_NOMEM : K16_ERR_HIP;
+}
+
+// rc, behind a drain of the stream where it is a failure: nothing of a scan stays in flight
+static int r1cs_scan_drained(k16_ctx* ctx, int rc)
+{
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+// A stage on first use: built into an owner of its own and installed only when it is whole.  After a failure nothing of it
+// remains -- the stream is drained before the owner releases what a copy may still write to -- and a later call starts over.
+template <class T, class F>
+static int r1cs_scan_stage(k16_ctx* ctx, std::unique_ptr<T>& slot, F&& make)
+{
+    if (slot) return K16_OK;
+    std::unique_ptr<T> fresh(new T());
+    const int          rc = r1cs_scan_drained(ctx, make(*fresh));
+    if (!rc) slot = std::move(fresh);
+    return rc;
+}
+
+// what the device list holds: all but wire 0's column, which stays on the host (see k_r1cs_incidences)
+static size_t r1cs_walked(const R1csPairs& P) { return P.pair.size() - P.start[1]; }
+
+// list, side table and mask on the device
+static int r1cs_scan_upload(k16_ctx* ctx, k16_r1cs* r, ScanList& S)
+{
+    const R1csPairs&    P    = r->scans->pairs;
+    const size_t        skip = P.start[1], n = r1cs_walked(P), words = P.present.size();
+    std::vector<R1csFr> side(P.side.size());
+    const R1csScale     to_r9(522);
+    for (size_t k = 0; k < side.size(); k++) side[k] = to_r9(P.side[k]);
+    int rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.inc, n * sizeof(R1csPair)))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.wire, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.side, side.size() * 32))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_bound, words * 8))) return rc;
+    K16_HIP(ctx, S.h_bound.alloc(std::max<size_t>(words * 8, 8)));
+    hipStream_t st = ctx->stream;
+    if (n) {
+        K16_HIP(ctx, hipMemcpyAsync(S.inc, P.pair.data() + skip, n * sizeof(R1csPair), hipMemcpyHostToDevice, st));
+        K16_HIP(ctx, hipMemcpyAsync(S.wire, P.wire.data() + skip, n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (!side.empty()) K16_HIP(ctx, hipMemcpyAsync(S.side, side.data(), side.size() * 32, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipStreamSynchronize(st)); // (side is a local)
+    return K16_OK;
+}
+
+// What every diagnostic starts with: a completed check to read, the host list, the device, the device list.
+static int r1cs_scan_begin(k16_ctx* ctx, k16_r1cs* r)
+{
+    if (!r->have_values || r->forked_on) {
+        ctx->err = "no completed check to scan";
+        return K16_ERR_ARG;
+    }
+    const int rc = r1cs_pairs_get(ctx, r);
+    if (rc) return rc;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    return r1cs_scan_stage(ctx, r->scans->list, [&](ScanList& S) { return r1cs_scan_upload(ctx, r, S); });
+}
+
+// the kernels' view of the device list and of the sums of the last completed check
+static IncList r1cs_inc_list(const k16_r1cs* r)
+{
+    const R1csPairs& P = r->scans->pairs;
+    const ScanList&  S = *r->scans->list;
+    return IncList{S.inc, S.wire, (uint32_t)r1cs_walked(P), r->d_coef, P.n_entries, S.side, r->d_rows, r->M};
+}
+static dim3 r1cs_blocks(uint64_t lanes) { return dim3((unsigned)((lanes + 255) / 256)); }
+
+// ---- the unbound-wire scan
+static int r1cs_scan_run(k16_ctx* ctx, k16_r1cs* r, const ScanList& S, size_t words)
+{
+    const IncList L  = r1cs_inc_list(r);
+    hipStream_t   st = ctx->stream;
+    K16_HIP(ctx, hipMemsetAsync(S.d_bound, 0, words * 8, st));
+    if (L.n_pairs) {
+        k16_stat_scope sc(ctx, "r1cs_incidences", st);
+        hipLaunchKernelGGL(k_r1cs_incidences, r1cs_blocks(L.n_pairs), dim3(256), 0, st, L, S.d_bound);
+    }
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(S.h_bound, S.d_bound, words * 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_unbound_wires(k16_r1cs* r, uint64_t* n_absent, uint64_t* n_unbound, uint32_t* h_wires, uint8_t* h_class,
+                                      uint32_t cap, uint8_t* h_status)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_absent || !n_unbound) return K16_ERR_ARG;
+    *n_absent = *n_unbound = 0;
+    k16_ctx* ctx = r->ctx;
+    int      rc  = r1cs_scan_begin(ctx, r);
+    if (rc) return rc;
+    const std::vector<uint64_t>& present = r->scans->pairs.present;
+    const ScanList&              S       = *r->scans->list;
+    if ((rc = r1cs_scan_drained(ctx, r1cs_scan_run(ctx, r, S, present.size())))) return rc;
+    r1cs_masks_unbound(r->n_wires, present.data(), S.h_bound, n_absent, n_unbound, h_wires, h_class, cap, h_status);
+    return K16_OK;
+    });
+}
+
+// ---- the second-value scan
+// masks, references, list and shifts; the incidence list itself is the unbound-wire scan's
+static int r1cs_second_alloc(k16_ctx* ctx, k16_r1cs* r, ScanSecond& S)
+{
+    const size_t words = r->scans->pairs.present.size(), n = r->n_wires;
+    int          rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_kinds, 2 * words * 8))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_ref, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_list, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_shift, n * 32))) return rc;
+    K16_HIP(ctx, S.h_kinds.alloc(std::max<size_t>(2 * words * 8, 8)));
+    K16_HIP(ctx, S.h_list.alloc(std::max<size_t>(n * 4, 8)));
+    return K16_OK;
+}
+
+static int r1cs_second_run(k16_ctx* ctx, k16_r1cs* r, uint64_t* n_two_valued, uint32_t* h_wires, uint8_t* h_shift, uint32_t cap,
+                           uint8_t* h_status)
+{
+    const ScanSecond& S     = *r->scans->second;
+    const IncList     L     = r1cs_inc_list(r);
+    const size_t      words = r->scans->pairs.present.size();
+    hipStream_t       st    = ctx->stream;
+    K16_HIP(ctx, hipMemsetAsync(S.d_kinds, 0, 2 * words * 8, st));
+    K16_HIP(ctx, hipMemsetAsync(S.d_ref, 0xff, (size_t)r->n_wires * 4, st));
+    if (L.n_pairs) {
+        {
+            k16_stat_scope sc(ctx, "r1cs_kinds", st);
+            hipLaunchKernelGGL(k_r1cs_kinds, r1cs_blocks(L.n_pairs), dim3(256), 0, st, L, S.d_kinds, S.d_kinds + words, S.d_ref);
+        }
+        {
+            k16_stat_scope sc(ctx, "r1cs_agree", st);
+            hipLaunchKernelGGL(k_r1cs_agree, r1cs_blocks(L.n_pairs), dim3(256), 0, st, L, S.d_ref, S.d_kinds);
+        }
+    }
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(S.h_kinds, S.d_kinds, 2 * words * 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    // the wires are listed for either output: the shifts are those of the listed wires
+    const uint32_t listed = r1cs_masks_second(r->n_wires, r->scans->pairs.present.data(), S.h_kinds, S.h_kinds + words, n_two_valued,
+                                              h_wires || h_shift ? S.h_list.p : nullptr, cap, h_status);
+    if (h_wires && listed) memcpy(h_wires, S.h_list, (size_t)listed * 4);
+    if (h_shift && listed) {
+        K16_HIP(ctx, hipMemcpyAsync(S.d_list, S.h_list, (size_t)listed * 4, hipMemcpyHostToDevice, st));
+        {
+            k16_stat_scope sc(ctx, "r1cs_shifts", st);
+            hipLaunchKernelGGL(k_r1cs_shifts, dim3((listed + 63) / 64), dim3(64), 0, st, S.d_list, listed, L, S.d_ref, S.d_shift);
+        }
+        K16_HIP(ctx, hipGetLastError());
+        K16_HIP(ctx, hipMemcpyAsync(h_shift, S.d_shift, (size_t)listed * 32, hipMemcpyDeviceToHost, st));
+        K16_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_second_values(k16_r1cs* r, uint64_t* n_two_valued, uint32_t* h_wires, uint8_t* h_shift, uint32_t cap,
+                                      uint8_t* h_status)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_two_valued) return K16_ERR_ARG;
+    *n_two_valued = 0;
+    k16_ctx* ctx  = r->ctx;
+    int      rc   = r1cs_scan_begin(ctx, r);
+    if (rc) return rc;
+    if ((rc = r1cs_scan_stage(ctx, r->scans->second, [&](ScanSecond& S) { return r1cs_second_alloc(ctx, r, S); }))) return rc;
+    if ((rc = r1cs_scan_drained(ctx, r1cs_second_run(ctx, r, n_two_valued, h_wires, h_shift, cap, h_status)))) *n_two_valued = 0;
+    return rc;
+    });
+}
+
+// ---- the determinism closure
+// column starts, masks, the two words per constraint, the maps and the two lists
+static int r1cs_det_alloc(k16_ctx* ctx, k16_r1cs* r, ScanDet& S)
+{
+    const R1csPairs& P     = r->scans->pairs;
+    const size_t     words = P.present.size(), n = r->n_wires, M = r->M;
+    int              rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_start, (n + 1) * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_masks, 2 * words * 8))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_cnt, 2 * M * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_by, 2 * n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_cand, M * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_front, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_state, sizeof(DetState)))) return rc;
+    K16_HIP(ctx, S.h_masks.alloc(std::max<size_t>(2 * words * 8, 8)));
+    K16_HIP(ctx, S.rec.alloc(sizeof(DetRecord), hipHostMallocMapped | hipHostMallocCoherent));
+    // the device list leaves wire 0's column out: its columns start that much lower
+    const uint32_t        skip = P.start[1];
+    std::vector<uint32_t> start(n + 1);
+    for (size_t i = 0; i <= n; i++) start[i] = std::max(P.start[i], skip) - skip;
+    K16_HIP(ctx, hipMemcpyAsync(S.d_start, start.data(), (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    K16_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (start is a local)
+    return K16_OK;
+}
+
+// h_masks[0 .. words) holds the seed.  Leaves `known` in h_masks[words ..); round and by as the device left them
+// (r1cs_masks_closure writes round 0 for the seed) where asked for.
+static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by)
+{
+    const ScanDet&   S     = *r->scans->det;
+    const IncList    L     = r1cs_inc_list(r);
+    const size_t     words = r->scans->pairs.present.size();
+    const uint32_t   M = r->M, n_wires = r->n_wires;
+    hipStream_t      st = ctx->stream;
+    unsigned long long *d_seed = S.d_masks, *d_known = S.d_masks + words;
+    uint32_t *          d_cnt = S.d_cnt, *d_xr = S.d_cnt + M, *d_by = S.d_by, *d_round = S.d_by + n_wires;
+    auto capped = [](uint64_t lanes) { return dim3((unsigned)std::min<uint64_t>((lanes + 255) / 256, DET_GRID)); };
+    *n_rounds   = 0;
+    S.rec->n_front = S.rec->n_cand = 0;
+    K16_HIP(ctx, hipMemcpyAsync(d_seed, S.h_masks, words * 8, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(d_known, S.h_masks, words * 8, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemsetAsync(S.d_by, 0xff, 2 * (size_t)n_wires * 4, st));
+    K16_HIP(ctx, hipMemsetAsync(S.d_state, 0, sizeof(DetState), st));
+    if (L.n_pairs && M) {
+        K16_HIP(ctx, hipMemsetAsync(S.d_cnt, 0, 2 * (size_t)M * 4, st));
+        {
+            k16_stat_scope sc(ctx, "r1cs_det_init", st);
+            hipLaunchKernelGGL(k_r1cs_det_init, r1cs_blocks(L.n_pairs), dim3(256), 0, st, L, n_wires, d_seed, d_cnt, d_xr);
+            hipLaunchKernelGGL(k_r1cs_det_first, capped(M), dim3(256), 0, st, d_cnt, M, S.d_cand, S.d_state, S.rec.dev);
+        }
+        K16_HIP(ctx, hipGetLastError());
+    }
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    // round k judges the candidates [c0, c1) and derives the frontier [f0, f1)
+    uint32_t c0 = 0, c1 = S.rec->n_cand, f0 = 0, round = 0;
+    while (c1 > c0) {
+        // every round that goes on adds a wire, and wire 0 is never added: at most n_wires - 1 rounds
+        if (round + 1 >= n_wires || c1 > M) {
+            ctx->err = "determinism closure: more rounds than wires";
+            return K16_ERR_HIP;
+        }
+        round++;
+        {
+            k16_stat_scope sc(ctx, "r1cs_det_derive", st);
+            hipLaunchKernelGGL(k_r1cs_det_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, r->d_mask, d_known,
+                               d_cnt, d_xr, n_wires, d_by, S.d_front, S.d_state);
+        }
+        {
+            // a candidate derives one wire at the most: the frontier is no longer than the candidates' range
+            k16_stat_scope sc(ctx, "r1cs_det_expand", st);
+            hipLaunchKernelGGL(k_r1cs_det_expand, capped(c1 - c0), dim3(256), 0, st, S.d_front, f0, round, S.d_start, L, n_wires,
+                               d_known, d_round, d_cnt, d_xr, S.d_cand, S.d_state, S.rec.dev);
+        }
+        K16_HIP(ctx, hipGetLastError());
+        K16_HIP(ctx, hipStreamSynchronize(st));
+        const uint32_t f1 = S.rec->n_front, c2 = S.rec->n_cand;
+        if (f1 < f0 || f1 > n_wires || c2 < c1) {
+            ctx->err = "determinism closure: a list shrank or outgrew its room";
+            return K16_ERR_HIP;
+        }
+        if (f1 == f0) { // nothing derived: the level before was the fixed point
+            round--;
+            break;
+        }
+        f0 = f1, c0 = c1, c1 = c2;
+    }
+    *n_rounds = round;
+    K16_HIP(ctx, hipMemcpyAsync(S.h_masks + words, d_known, words * 8, hipMemcpyDeviceToHost, st));
+    if (h_by) K16_HIP(ctx, hipMemcpyAsync(h_by, d_by, (size_t)n_wires * 4, hipMemcpyDeviceToHost, st));
+    if (h_round) K16_HIP(ctx, hipMemcpyAsync(h_round, d_round, (size_t)n_wires * 4, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_determined_wires(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_seed, uint64_t* n_derived, uint64_t* n_absent,
+                                         uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
+                                         uint32_t* h_round, uint32_t* h_by)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_derived || !n_absent || !n_open || !n_rounds || (!h_seed && n_seed)) return K16_ERR_ARG;
+    *n_derived = *n_absent = *n_open = 0;
+    *n_rounds                        = 0;
+    k16_ctx* ctx                     = r->ctx;
+    int      rc                      = r1cs_scan_begin(ctx, r);
+    if (rc) return rc;
+    if ((rc = r1cs_scan_stage(ctx, r->scans->det, [&](ScanDet& S) { return r1cs_det_alloc(ctx, r, S); }))) return rc;
+    const ScanDet& S     = *r->scans->det;
+    const size_t   words = r->scans->pairs.present.size();
+    if (const char* why = r1cs_seed_mask(r->n_wires, r->file.n_pub_out, r->file.n_pub_in, r->file.n_prv_in, h_seed, n_seed, S.h_masks)) {
+        ctx->err = why;
+        return K16_ERR_ARG;
+    }
+    if ((rc = r1cs_scan_drained(ctx, r1cs_det_run(ctx, r, n_rounds, h_round, h_by)))) {
+        *n_rounds = 0;
+        return rc;
+    }
+    const uint64_t* present = r->scans->pairs.present.data();
+    r1cs_masks_closure(r->n_wires, present, S.h_masks, S.h_masks + words, n_derived, n_absent, n_open, h_wires, cap, h_status, h_round);
+    return K16_OK;
+    });
+}
+
+// ---- the list itself
+extern "C" int k16_r1cs_wire_constraints(k16_r1cs* r, uint32_t wire, uint64_t* n, uint32_t* h_constraints, uint32_t cap)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n) return K16_ERR_ARG;
+    *n = 0;
+    if (wire >= r->n_wires) {
+        r->ctx->err = "wire number out of range";
+        return K16_ERR_ARG;
+    }
+    const int rc = r1cs_pairs_get(r->ctx, r);
+    if (rc) return rc;
+    const R1csPairs& P = r->scans->pairs;
+    *n                 = P.start[wire + 1] - P.start[wire];
+    const uint64_t k_n = std::min<uint64_t>(*n, cap);
+    for (uint64_t k = 0; h_constraints && k < k_n; k++) h_constraints[k] = P.pair[P.start[wire] + k].constraint;
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_r1cs_incidences(k16_r1cs* r, uint64_t* n_pairs)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_pairs) return K16_ERR_ARG;
+    *n_pairs     = 0;
+    const int rc = r1cs_pairs_get(r->ctx, r);
+    if (rc) return rc;
+    *n_pairs = r->scans->pairs.n_pairs();
+    return K16_OK;
+    });
+}

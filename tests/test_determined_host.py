@@ -1,6 +1,7 @@
 """The reference of the determinism closure and its certificate replayer (tests/determined_reference.py) on circuits worked by
-hand, and the argument checks of the binding that need no device.  No GPU.  k16_r1cs_determined_wires adds no host-only header
-code (the seed mask is built inside the call, in csrc/r1cs_check.hip), so there is no stand-alone C++ program for it."""
+hand, and the argument checks of the binding that need no device.  No GPU.  The host-only code of k16_r1cs_determined_wires
+(the seed mask and the walk over the closure's masks, csrc/r1cs_masks.h) has its stand-alone C++ program in
+tests/test_r1cs_masks_host.py."""
 import pytest
 
 import determined_reference as dr

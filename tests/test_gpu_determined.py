@@ -1,4 +1,4 @@
-"""-m gpu : the determinism closure (include/k16.h k16_r1cs_determined_wires; csrc/r1cs_check.hip k_r1cs_det_init, _first,
+"""-m gpu : the determinism closure (include/k16.h k16_r1cs_determined_wires; csrc/r1cs_scan.hip k_r1cs_det_init, _first,
 _derive, _expand) against the big-integer reference of tests/determined_reference.py.  Every case compares the counts, the
 ascending OPEN list and the status, round and by of every wire with the reference, and runs the reference's independent
 certificate replayer on the GPU's own output; what the directed circuits must give is stated by hand there and asserted of the

@@ -1,4 +1,4 @@
-"""-m gpu : the second-value scan (include/k16.h k16_r1cs_second_values; csrc/r1cs_check.hip k_r1cs_kinds, k_r1cs_agree,
+"""-m gpu : the second-value scan (include/k16.h k16_r1cs_second_values; csrc/r1cs_scan.hip k_r1cs_kinds, k_r1cs_agree,
 k_r1cs_shifts) against the big-integer reference of tests/second_value_reference.py.  Every case compares the class of every
 wire, the count, the ascending list and the shifts' bytes with the reference; what each directed circuit's classes and shifts
 must be is stated by hand there and asserted of the reference in tests/test_second_value_host.py."""

@@ -1,4 +1,4 @@
-"""-m gpu : the unbound-wire scan (include/k16.h k16_r1cs_unbound_wires / _wire_constraints / _incidences; csrc/r1cs_check.hip
+"""-m gpu : the unbound-wire scan (include/k16.h k16_r1cs_unbound_wires / _wire_constraints / _incidences; csrc/r1cs_scan.hip
 k_r1cs_incidences, csrc/r1cs_pairs.h) against the big-integer reference of tests/unbound_reference.py.  Every case compares the
 class of every wire, both counts and the ascending list with the reference; what each directed circuit's classes must be is
 asserted of the reference itself in tests/test_unbound_host.py."""

@@ -2,8 +2,8 @@
     python tools/ab_r1cs_paths.py --parent-pkg DIR --out FILE.json [--rounds 5]
 DIR holds k16.py and libk16.so of the parent commit.  Per round and side one fresh process each for
     check    the legs of tools/bench_r1cs_check.py: prove_mem_verified, k16_r1cs_check_mem, k16_r1cs_check_prover_witness,
-             and behind them the two scans of the sums, k16_r1cs_unbound_wires and k16_r1cs_second_values (cap 64),
-             alternating call by call, 50 calls per leg
+             and behind them the diagnostics of the sums, k16_r1cs_unbound_wires, k16_r1cs_second_values (cap 64) and
+             k16_r1cs_determined_wires (the default seed, cap 64, no maps), alternating call by call, 50 calls per leg
     checked  the child mode of tools/bench_prove_checked.py (legs a, b, c: prove_mem_verified unattached, with the circuit
              attached, and followed by the stand-alone check), 60 proofs per leg
 on the synthetic key of the Keyless shape those tools use, built once; the sides alternate.  Per leg: the p50 of the round
@@ -89,7 +89,17 @@ def check_child(d, pkg, calls=50, warmup=5):
         assert rc == 0 and n2.value > 0
         return ms
 
-    legs = [("prove", leg_prove), ("mem", leg_mem), ("prover", leg_prover), ("unbound", leg_unbound), ("second", leg_second)]
+    nd, nab, no, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+
+    def leg_closure(i):
+        t = time.perf_counter()
+        rc = L.k16_r1cs_determined_wires(circ.h, None, 0, C.byref(nd), C.byref(nab), C.byref(no), C.byref(nr), _p(free_w), 64, None, None, None)
+        ms = (time.perf_counter() - t) * 1e3
+        assert rc == 0
+        return ms
+
+    legs = [("prove", leg_prove), ("mem", leg_mem), ("prover", leg_prover), ("unbound", leg_unbound), ("second", leg_second),
+            ("closure", leg_closure)]
     for k in range(warmup):
         for _, fn in legs:
             fn(k % len(wtns))
@@ -155,16 +165,16 @@ def main():
                 }
             rounds.append(row)
             print("round %d  " % rnd + "   ".join(
-                "%s: check prover %.4f mem %.4f unbound %.4f second %.4f  prove a %.3f b(attached) %.3f c %.3f" % (
+                "%s: check prover %.4f mem %.4f unbound %.4f second %.4f closure %.4f  prove a %.3f b(attached) %.3f c %.3f" % (
                     side, row[side]["check"]["prover"]["p50_ms"], row[side]["check"]["mem"]["p50_ms"],
-                    row[side]["check"]["unbound"]["p50_ms"], row[side]["check"]["second"]["p50_ms"],
+                    row[side]["check"]["unbound"]["p50_ms"], row[side]["check"]["second"]["p50_ms"], row[side]["check"]["closure"]["p50_ms"],
                     row[side]["checked"]["a"]["p50_ms"], row[side]["checked"]["b"]["p50_ms"], row[side]["checked"]["c"]["p50_ms"])
                 for side in ("parent", "tree")), flush=True)
         summ = {}
         for side in ("parent", "tree"):
             summ[side] = {}
             for what, grp, leg in (("check_prover_witness", "check", "prover"), ("check_mem", "check", "mem"),
-                                   ("unbound_wires", "check", "unbound"), ("second_values", "check", "second"),
+                                   ("unbound_wires", "check", "unbound"), ("second_values", "check", "second"), ("determined_wires", "check", "closure"),
                                    ("prove_verified_unattached", "checked", "a"), ("prove_verified_attached", "checked", "b")):
                 xs = [r[side][grp][leg]["p50_ms"] for r in rounds]
                 summ[side][what] = {"p50_of_rounds_ms": statistics.median(xs), "spread_ms": [min(xs), max(xs)]}
