@@ -673,6 +673,57 @@ int  k16_r1cs_determined_wires(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_s
                                uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
                                uint32_t* h_round, uint32_t* h_by);
 
+/* ---- witness completion: WHICH VALUES do the given wires force? ----
+ * The closure above names the wires a seed forces; this call computes them.  It takes the circuit, the GIVEN wires G and their
+ * values (wire 0 is always given and must be 1), K_0 = G + {0}, and applies, level by level,
+ *     in constraint c exactly one wire x with a non-zero merged coefficient (A^, B^, C^ as in the scans) lies outside K_k; with
+ *     a0, b0, c0 the sums of c's three combinations over its wires in K_k, the residual of c as a polynomial in x is
+ *     quad x^2 + lin x + k0,  quad = A^ B^,  lin = A^ b0 + B^ a0 - C^,  k0 = a0 b0 - c0  (mod r);
+ *     quad = 0 and lin != 0   ==>   x joins K_k+1 with the value -k0 / lin
+ * Otherwise c gives nothing: quad != 0 leaves a quadratic (no square root is taken), lin = 0 means c does not depend on x.
+ * round[x] = k + 1; by[x] is the LOWEST c the rule holds for with respect to K_k, and the value is that constraint's.  The result
+ * is a function of circuit, givens and their values alone: exact, deterministic, the same bytes on every run.
+ *   K16_SOLVE_GIVEN   in G (or wire 0)
+ *   K16_SOLVE_SOLVED  in K, not given
+ *   K16_SOLVE_ABSENT  not in K and in no term
+ *   K16_SOLVE_OPEN    not in K and in some term
+ * numbered as K16_DET_*: the two maps compare directly.
+ * RETURNED ASSIGNMENT (h_wtns, n_wires x 32 B standard form, in and out): given wires keep their values, solved wires get
+ * theirs in canonical standard form, ABSENT and OPEN wires are written as 0.  What the caller had in the positions outside G is
+ * ignored: any bytes, values >= r included.
+ * VERDICT: a constraint with no wire outside the final K is CLOSED and is judged on the returned assignment.  *n_failed = the
+ * number of closed constraints that are broken, h_failed (may be NULL) the lowest min(*n_failed, cap_failed) of them, ascending;
+ * a constraint that would have given an already solved wire a different value shows up here.  *n_open_constraints counts the
+ * rest; they are not judged.
+ * SOUND: every satisfying witness that agrees with the givens agrees with every solved value (with quad = 0 and lin != 0 the
+ * root is unique).  *n_failed > 0 proves that NO satisfying witness has these given values.  *n_open == 0 && *n_failed == 0:
+ * the returned bytes are a satisfying witness, and the only one with these givens.
+ * NOT COMPLETE, in two ways, and the call judges nothing beyond this: an OPEN wire may still be forced by an argument over
+ * several constraints, or by a quadratic; and a constraint with lin = 0, k0 != 0 whose one wire is never solved stays unjudged,
+ * although nothing satisfies it.
+ *   h_given / n_given   the given wires; duplicates are legal, wire 0 is added.  NULL: the default seed of
+ *                       k16_r1cs_determined_wires (wire 0 and the header's inputs), K16_ERR_ARG when the header's counts reach
+ *                       beyond nWires
+ *   *n_solved, *n_absent, *n_open, *n_rounds, *n_failed, *n_open_constraints   required; zeroed on entry
+ *   h_wires (may be NULL)   the lowest min(*n_open, cap) OPEN wires, ascending
+ *   h_status, h_round, h_by (may be NULL)   as k16_r1cs_determined_wires: class, round (0 for a given wire) and solving
+ *                       constraint of every wire, 0xffffffff where there is none
+ * ERRORS: K16_ERR_ARG when a given wire is >= nWires (nothing is launched, no list, map or witness byte is written);
+ * K16_ERR_FORMAT when a GIVEN value is >= r or wire 0's value is not 1, as in k16_r1cs_check_* (h_wtns, lists and maps stay
+ * untouched); K16_ERR_ARG while a prove call runs on an attached object -- the call is legal between prove calls.  Every error
+ * leaves nothing in flight.  THREADING as k16_r1cs_check_*.
+ * STATE: the call needs no completed check and ends with one: after K16_OK the object is in the state k16_r1cs_check_mem on the
+ * returned h_wtns would leave -- k16_r1cs_last_values, both scans and the closure read the sums of the returned assignment.
+ * After an error the object holds no completed check.
+ * One host synchronise per round, as the closure; the row view of the circuit (8 bytes a term) is uploaded by the first call and
+ * stays with the object, the incidence list is the scans' (csrc/r1cs_scan.hip). */
+enum { K16_SOLVE_GIVEN = 0, K16_SOLVE_SOLVED = 1, K16_SOLVE_ABSENT = 2, K16_SOLVE_OPEN = 3 };
+int  k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns /* n_wires x 32 B standard form, in and out */, const uint32_t* h_given,
+                               uint32_t n_given, uint64_t* n_solved, uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds,
+                               uint64_t* n_failed, uint32_t* h_failed, uint32_t cap_failed, uint64_t* n_open_constraints,
+                               uint32_t* h_wires /* lowest min(*n_open, cap) OPEN wires, ascending */, uint32_t cap, uint8_t* h_status,
+                               uint32_t* h_round, uint32_t* h_by);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

@@ -327,6 +327,10 @@ int  k16_r1cs_attach(k16_r1cs* r, k16_ctx* ctx, uint32_t n_vars, uint32_t n_publ
 int  k16_r1cs_fork(k16_r1cs* r, hipStream_t st, const k16::Fr* d_wtns, const uint16_t* d_n16);
 int  k16_r1cs_join(k16_r1cs* r, int* status, uint64_t* n_failed, uint32_t* lowest);
 void k16_r1cs_drain(k16_r1cs* r);
+// The three kernels of a check (k_r1cs_wtns, _rows, _judge) enqueued on st for the n_wires standard-form values at d_wtns: sums
+// into d_rows, verdicts and witness flags into d_mask, the 16-bit words into d_n16.  Nothing is copied or waited for, and
+// have_values is the caller's to set (r1cs_scan.hip: the closing pass of k16_r1cs_complete_witness).
+int  k16_r1cs_launch(k16_r1cs* r, hipStream_t st, const k16::Fr* d_wtns);
 
 // host-side helpers implemented in ntt.hip
 int k16_ntt_get_table(k16_ctx* ctx, uint64_t max_domain, k16_ntt_table** out);

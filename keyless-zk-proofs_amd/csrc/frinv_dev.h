@@ -1,4 +1,4 @@
-// frinv_dev.h -- the device Fr inversion the set-up (setup.hip) and the second-value scan (r1cs_check.hip) share.
+// frinv_dev.h -- the device Fr inversion the set-up (setup.hip), the second-value scan and the witness completion (r1cs_scan.hip) share.
 #pragma once
 #include "bn254_fq9.h"
 

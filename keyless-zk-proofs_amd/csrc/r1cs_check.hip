@@ -30,8 +30,6 @@ static_assert(R1CS_ERR_ARG == K16_ERR_ARG && R1CS_ERR_FORMAT == K16_ERR_FORMAT &
 
 namespace {
 
-enum : unsigned long long { WTNS_NOT_BELOW_R = 1, WTNS_WIRE0_NOT_ONE = 2 };
-
 // every wire: below r? wire 0: one?  n16 (may be null: the prover made it already) as k_wtns_n16 of prover.hip makes it
 __global__ void __launch_bounds__(256) k_r1cs_wtns(const uint4* __restrict__ wtns, uint32_t n, uint16_t* __restrict__ n16,
                                                    unsigned long long* __restrict__ flags)
@@ -249,6 +247,8 @@ static int r1cs_launch(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint16
     K16_HIP(ctx, hipGetLastError());
     return K16_OK;
 }
+
+int k16_r1cs_launch(k16_r1cs* r, hipStream_t st, const Fr* d_wtns) { return r1cs_launch(r->ctx, r, d_wtns, nullptr, st); }
 
 // The check proper, on the context's stream.  Whatever fails, the stream is drained before the caller returns.
 static int r1cs_enqueue(k16_ctx* ctx, k16_r1cs* r, const Fr* d_wtns, const uint16_t* d_n16)

@@ -36,6 +36,9 @@ struct PinnedBuf {
     T* operator->() const { return p; }
 };
 
+// why a witness is refused (k_r1cs_wtns; the witness completion's k_r1cs_solve_mask): bits of the flag word behind the verdicts
+enum : unsigned long long { WTNS_NOT_BELOW_R = 1, WTNS_WIRE0_NOT_ONE = 2 };
+
 // What a prove call keeps of its check (pinned, device-mapped; read by the host after the check is joined).
 struct CheckRecord {
     unsigned long long flags;                       // WTNS_* of k_r1cs_wtns
@@ -43,7 +46,7 @@ struct CheckRecord {
     uint32_t           lowest[K16_R1CS_REPORT_MAX]; // the lowest min(count, K16_R1CS_REPORT_MAX) of them, ascending
 };
 
-struct R1csScans; // r1cs_scan.hip: the host list, the device list, the second-value and the closure buffers
+struct R1csScans; // r1cs_scan.hip: the host list, the device list, the second-value, the closure and the completion buffers
 void r1cs_scans_delete(R1csScans* s);
 
 } // namespace k16

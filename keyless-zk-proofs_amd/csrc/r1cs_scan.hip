@@ -4,6 +4,7 @@
 //   k16_r1cs_unbound_wires     which wires could take any value without moving a residual?  k_r1cs_incidences
 //   k16_r1cs_second_values     which admit exactly ONE other value, every other wire held fixed?  k_r1cs_kinds, _agree, _shifts (10c)
 //   k16_r1cs_determined_wires  which does the circuit force, given the seed wires?  k_r1cs_det_init, _first, _derive, _expand (10d)
+//   k16_r1cs_complete_witness  which VALUES do the given wires force?  the closure's frontier + k_r1cs_solve_mask, _derive, _commit, _close (10e)
 // Each kernel is described where it stands.  The list and every buffer here are made by the first call that needs them: create
 // and check calls allocate and launch nothing of this file.  From masks to counts, lists and status bytes: r1cs_masks.h.
 #include <string.h>
@@ -14,11 +15,13 @@
 #include "frinv_dev.h"
 #include "r1cs_masks.h"
 #include "r1cs_pairs.h"
+#include "r1cs_rows.h"
 #include "spmv_dev.h"
 
 using namespace k16;
 
 static_assert(sizeof(R1csPair) == sizeof(uint4), "an incidence is one 16-byte load");
+static_assert(sizeof(R1csRowRef) == sizeof(uint2), "a term of the row view is one 8-byte load");
 
 namespace {
 
@@ -380,7 +383,181 @@ __global__ void __launch_bounds__(256) k_r1cs_det_expand(const uint32_t* __restr
     det_publish(st, rec);
 }
 
-// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Three stages, each made whole by the first call
+// The witness completion (k16_r1cs_complete_witness): the closure's frontier with VALUES.  K_0 holds the
+// given wires; with respect to K_k a constraint c with exactly ONE incidence (x, c) outside is a polynomial in x,
+//     quad x^2 + lin x + k0,   quad = A^ B^,  lin = A^ b0 + B^ a0 - C^,  k0 = a0 b0 - c0
+// a0, b0, c0 being the sums of c's three rows over its wires in K_k; quad = 0 and lin != 0 give x = -k0 / lin, anything else
+// gives nothing.  cnt, xr, the two lists, the record and the kernels k_r1cs_det_init, _first and _expand are the closure's.
+// INVARIANT: a wire outside K holds 0 in wtns.  A plain sum over a row IS the sum over its wires in K, x's own terms add
+// nothing, and a wire whose coefficients cancel inside a row needs no special case.
+//   k_r1cs_solve_mask    one lane per wire: outside the givens -> 0 (whatever the caller had there), a given value >= r or
+//                        wire 0 != 1 -> the flag word: the host reads it before the first round
+//   k_r1cs_solve_derive  one lane per candidate of this round: cnt still 1, the outside incidence names not both A^ and B^
+//                        (quad != 0 otherwise, see inc_terms: no product needed), three row sums through the row view, lin != 0
+//                        -> the value into val[c], atomicMin(by[x], c), the first claim appends x to the frontier
+//   k_r1cs_solve_commit  one lane per frontier wire of this round: wtns[x] = val[by[x]]
+//   k_r1cs_det_expand    as in the closure
+//   k_r1cs_solve_close   after the fixed point and the check's own kernels on wtns: one lane per constraint, cnt != 0 -> open;
+//                        the verdicts of the open constraints are taken out
+// THE COMMIT HAZARD: two candidates of one round may claim the same x with different values (then no witness agrees with the
+// givens).  by[x] is a minimum and ends the same in every launch order; a value stored by the claiming lane would be the LAST
+// claimer's, not the lowest's.  So a candidate keeps its value in a slot of its own -- val[c]: a constraint is a candidate once
+// -- and wtns[x] is written by the next kernel, when by[x] is final.  wtns is only read in k_r1cs_solve_derive, and 0 is a value
+// like any other: what is known is the `known` mask's to say, never the value's.
+// Scalings (see inc_terms): a coefficient k lies in coef / side as k 2^522, a wire's value v in wtns in standard form, v < r.
+//   term  frmul9(k 2^522, v) = k v 2^261, the R' value of the product, < 2r; fradd9 keeps a sum < 2r: a0, b0, c0 are R' values,
+//         exactly what k_r1cs_rows leaves in d_rows
+//   lin   frmul9(A^ 2^522, b0 2^261) = A^ b0 2^522 (or B^ a0; never both: quad = 0), frsub9 with C^ 2^522 < r: lin 2^522,
+//         the value inc_terms forms, on these sums.  fr9_nonzero: zero exactly when r divides lin
+//   k0    frmul9(a0 2^261, b0 2^261) = a0 b0 2^261, frsub9 with c0 2^261 < 2r: k0 2^261, an R' value
+//   x     frmul9(lin 2^522, 1) = lin 2^261, the R' value of lin; frinv9 returns the R' value of its inverse, lin^-1 2^261;
+//         frmul9(k0 2^261, lin^-1 2^261) = (k0 / lin) 2^261, negated by frsub9(0, .) and brought to the canonical standard form
+//         by fr9_to_standard: the bytes that go into wtns and back to the caller.
+constexpr uint32_t SOLVE_SHORT = 16; // terms in the three rows of a candidate up to which its lane walks them alone
+
+// The device row view (r1cs_rows.h): start[3 M + 1], term[t].x the wire, .y the position of the coefficient in coef.
+struct RowView {
+    const uint32_t* __restrict__ start;
+    const uint2* __restrict__ term;
+};
+__device__ __forceinline__ Fr9 solve_term(const RowView& V, const IncList& L, const Fr* __restrict__ wtns, uint32_t n_wires, uint32_t t)
+{
+    const uint2 e = V.term[t];
+    if (e.x >= n_wires || e.y >= L.n_entries) return fq9_zero();
+    return frmul9(ld_r9(&L.coef[e.y]), ld_r9(&wtns[e.x]));
+}
+
+// given: ceil(n_wires / 64) words; flags: one word, cleared before the launch (WTNS_*, as k_r1cs_wtns sets them)
+__global__ void __launch_bounds__(256) k_r1cs_solve_mask(uint4* __restrict__ wtns, uint32_t n_wires, const unsigned long long* __restrict__ given,
+                                                         unsigned long long* __restrict__ flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_wires) return;
+    if (!det_bit(given, i)) {
+        wtns[2 * (size_t)i] = wtns[2 * (size_t)i + 1] = make_uint4(0, 0, 0, 0);
+        return;
+    }
+    const uint4        lo = wtns[2 * (size_t)i], hi = wtns[2 * (size_t)i + 1];
+    const uint32_t     v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    unsigned long long bad  = 0;
+    bool               geq  = true; // v >= r?
+    for (int k = 7; k >= 0; k--) {
+        if (v[k] != FrParams::P[k]) {
+            geq = v[k] > FrParams::P[k];
+            break;
+        }
+    }
+    if (geq) bad |= WTNS_NOT_BELOW_R;
+    if (i == 0 && (v[0] != 1u || (v[1] | v[2] | v[3] | v[4] | v[5] | v[6] | v[7]) != 0)) bad |= WTNS_WIRE0_NOT_ONE;
+    if (bad) atomicOr(flags, bad);
+}
+
+// cand[0 .. n): the candidates of this round.  val: M slots.  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_solve_derive(const uint32_t* __restrict__ cand, uint32_t n, const IncList L, const RowView V,
+                                                           const Fr* __restrict__ wtns, const unsigned long long* __restrict__ known,
+                                                           const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ xr, uint32_t n_wires,
+                                                           uint32_t* by, Fr* __restrict__ val, uint32_t* __restrict__ front, DetState* st)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
+    bool           live = false;
+    uint32_t       c = 0, x = 0;
+    uint4          e = make_uint4(0, R1CS_PAIR_NONE, R1CS_PAIR_NONE, R1CS_PAIR_NONE);
+    if (k < n) {
+        c = cand[k];
+        if (c < L.M && cnt[c] == 1u) { // (a constraint may have fallen on to 0 in the expansion that listed it)
+            const uint32_t idx = xr[c];
+            if (idx < L.n_pairs) {
+                x    = L.wire[idx];
+                e    = L.inc[idx];
+                live = x < n_wires && e.x == c && !det_bit(known, x) && !(e.y != R1CS_PAIR_NONE && e.z != R1CS_PAIR_NONE);
+            }
+        }
+    }
+    // the three row sums: a short candidate by its lane, a long one by the whole wave, 64 terms a step
+    uint32_t s[3] = {0, 0, 0}, len[3] = {0, 0, 0};
+    Fr9      sum[3] = {fq9_zero(), fq9_zero(), fq9_zero()};
+    if (live) {
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            s[m]               = V.start[(size_t)m * L.M + c];
+            const uint32_t end = V.start[(size_t)m * L.M + c + 1];
+            len[m]             = end > s[m] ? end - s[m] : 0;
+        }
+    }
+    const uint32_t total = len[0] + len[1] + len[2];
+    if (live && total <= SOLVE_SHORT) {
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+            for (uint32_t t = 0; t < len[m]; t++) sum[m] = fradd9(sum[m], solve_term(V, L, wtns, n_wires, s[m] + t));
+    }
+    unsigned long long longs = __ballot(live && total > SOLVE_SHORT);
+    while (longs) {
+        const int src = __ffsll((long long)longs) - 1;
+        longs &= longs - 1;
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            const uint32_t ls = __shfl(s[m], src, 64), ll = __shfl(len[m], src, 64);
+            Fr9            acc = fq9_zero();
+            for (uint32_t t = lane; t < ll; t += 64u) acc = fradd9(acc, solve_term(V, L, wtns, n_wires, ls + t));
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                Fr9 o;
+#pragma unroll
+                for (int i = 0; i < 9; i++) o.l[i] = (uint32_t)__shfl_xor((int)acc.l[i], d, 64);
+                acc = fradd9(acc, o);
+            }
+            if ((int)lane == src) sum[m] = acc;
+        }
+    }
+    bool add = false;
+    if (live) {
+        Fr9 lin = fq9_zero();
+        if (e.y != R1CS_PAIR_NONE) lin = frmul9(L.at(e.y), sum[1]);
+        else if (e.z != R1CS_PAIR_NONE) lin = frmul9(L.at(e.z), sum[0]);
+        if (e.w != R1CS_PAIR_NONE) lin = frsub9(lin, L.at(e.w));
+        if (fr9_nonzero(lin)) {
+            Fr9 one  = fq9_zero();
+            one.l[0] = 1;
+            const Fr9 k0  = frsub9(frmul9(sum[0], sum[1]), sum[2]);
+            const Fr9 inv = frinv9(frmul9(lin, one));
+            st_fr(&val[c], fr9_to_standard(frsub9(fq9_zero(), frmul9(k0, inv))));
+            add = atomicMin(&by[x], c) == DET_NONE;
+        }
+    }
+    wave_append(front, &st->n_front, n_wires, add, x);
+}
+
+// front[from .. st->n_front): the wires this round solved; by is final for them (k_r1cs_solve_derive has ended).  A workgroup
+// strides them: any grid covers them.
+__global__ void __launch_bounds__(256) k_r1cs_solve_commit(const uint32_t* __restrict__ front, uint32_t from, const DetState* st,
+                                                           const uint32_t* __restrict__ by, const Fr* __restrict__ val, uint32_t n_wires,
+                                                           uint32_t M, Fr* __restrict__ wtns)
+{
+    const uint32_t total = __atomic_load_n(&st->n_front, __ATOMIC_RELAXED);
+    const uint32_t todo  = total > from ? total - from : 0;
+    for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < todo; k += (uint64_t)gridDim.x * 256u) {
+        const uint32_t x = front[from + k];
+        if (x >= n_wires) continue;
+        const uint32_t c = by[x];
+        if (c < M) st_fr(&wtns[x], ld_fr(&val[c]));
+    }
+}
+
+// verdict: the check's mask on the completed assignment.  judged / open: n_words words each; open bit c = constraint c still
+// has a wire outside K, judged = verdict without those.  Lanes beyond M vote 0.  Launched with whole waves.
+__global__ void __launch_bounds__(256) k_r1cs_solve_close(const unsigned long long* __restrict__ verdict, const uint32_t* __restrict__ cnt,
+                                                          uint32_t M, uint32_t n_words, unsigned long long* __restrict__ judged,
+                                                          unsigned long long* __restrict__ open)
+{
+    const uint32_t           i     = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long votes = __ballot(i < M && cnt[i] != 0u);
+    if ((threadIdx.x & 63u) == 0 && (i >> 6) < n_words) {
+        judged[i >> 6] = verdict[i >> 6] & ~votes;
+        open[i >> 6]   = votes;
+    }
+}
+
+// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Four stages, each made whole by the first call
 // that needs it and kept until the object goes; a stage is ready when its pointer is set.
 struct ScanList { // the list on the device, and the unbound-wire scan's mask
     DevBuf<uint4>                 inc;     // R1csPair of every incidence of the wires 1 .. n_wires - 1
@@ -407,6 +584,13 @@ struct ScanDet { // the determinism closure
     DevBuf<DetState>              d_state;
     PinnedBuf<DetRecord>          rec;     // pinned, device-mapped
 };
+struct ScanSolve { // the witness completion: on top of the closure's stage
+    DevBuf<uint32_t>              d_rowstart; // [3 M + 1] the row view
+    DevBuf<uint2>                 d_term;     // [n_terms]
+    DevBuf<Fr>                    d_val;      // [M] a candidate's value, standard form
+    DevBuf<unsigned long long>    d_close;    // judged | open, [n_words] each | [1] the flags of k_r1cs_solve_mask | [1] the check's
+    PinnedBuf<unsigned long long> h_close;
+};
 
 } // namespace
 
@@ -415,6 +599,7 @@ struct k16::R1csScans {
     std::unique_ptr<ScanList>   list;
     std::unique_ptr<ScanSecond> second;
     std::unique_ptr<ScanDet>    det;
+    std::unique_ptr<ScanSolve>  solve;
 };
 void k16::r1cs_scans_delete(R1csScans* s) { delete s; }
 
@@ -497,17 +682,22 @@ static int r1cs_scan_upload(k16_ctx* ctx, k16_r1cs* r, ScanList& S)
     return K16_OK;
 }
 
-// What every diagnostic starts with: a completed check to read, the host list, the device, the device list.
+// the host list, the device, the device list
+static int r1cs_scan_list(k16_ctx* ctx, k16_r1cs* r)
+{
+    const int rc = r1cs_pairs_get(ctx, r);
+    if (rc) return rc;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    return r1cs_scan_stage(ctx, r->scans->list, [&](ScanList& S) { return r1cs_scan_upload(ctx, r, S); });
+}
+// What every diagnostic starts with: a completed check to read, and the list.
 static int r1cs_scan_begin(k16_ctx* ctx, k16_r1cs* r)
 {
     if (!r->have_values || r->forked_on) {
         ctx->err = "no completed check to scan";
         return K16_ERR_ARG;
     }
-    const int rc = r1cs_pairs_get(ctx, r);
-    if (rc) return rc;
-    K16_HIP(ctx, hipSetDevice(ctx->device));
-    return r1cs_scan_stage(ctx, r->scans->list, [&](ScanList& S) { return r1cs_scan_upload(ctx, r, S); });
+    return r1cs_scan_list(ctx, r);
 }
 
 // the kernels' view of the device list and of the sums of the last completed check
@@ -646,9 +836,10 @@ static int r1cs_det_alloc(k16_ctx* ctx, k16_r1cs* r, ScanDet& S)
     return K16_OK;
 }
 
-// h_masks[0 .. words) holds the seed.  Leaves `known` in h_masks[words ..); round and by as the device left them
-// (r1cs_masks_closure writes round 0 for the seed) where asked for.
-static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by)
+static dim3 r1cs_capped(uint64_t lanes) { return dim3((unsigned)std::min<uint64_t>((lanes + 255) / 256, DET_GRID)); }
+
+// h_masks[0 .. words) holds the seed: masks, maps, lists and the two words per constraint as round 1 finds them.  Enqueues only.
+static int r1cs_det_seed(k16_ctx* ctx, k16_r1cs* r)
 {
     const ScanDet&   S     = *r->scans->det;
     const IncList    L     = r1cs_inc_list(r);
@@ -656,9 +847,6 @@ static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t*
     const uint32_t   M = r->M, n_wires = r->n_wires;
     hipStream_t      st = ctx->stream;
     unsigned long long *d_seed = S.d_masks, *d_known = S.d_masks + words;
-    uint32_t *          d_cnt = S.d_cnt, *d_xr = S.d_cnt + M, *d_by = S.d_by, *d_round = S.d_by + n_wires;
-    auto capped = [](uint64_t lanes) { return dim3((unsigned)std::min<uint64_t>((lanes + 255) / 256, DET_GRID)); };
-    *n_rounds   = 0;
     S.rec->n_front = S.rec->n_cand = 0;
     K16_HIP(ctx, hipMemcpyAsync(d_seed, S.h_masks, words * 8, hipMemcpyHostToDevice, st));
     K16_HIP(ctx, hipMemcpyAsync(d_known, S.h_masks, words * 8, hipMemcpyHostToDevice, st));
@@ -668,11 +856,27 @@ static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t*
         K16_HIP(ctx, hipMemsetAsync(S.d_cnt, 0, 2 * (size_t)M * 4, st));
         {
             k16_stat_scope sc(ctx, "r1cs_det_init", st);
-            hipLaunchKernelGGL(k_r1cs_det_init, r1cs_blocks(L.n_pairs), dim3(256), 0, st, L, n_wires, d_seed, d_cnt, d_xr);
-            hipLaunchKernelGGL(k_r1cs_det_first, capped(M), dim3(256), 0, st, d_cnt, M, S.d_cand, S.d_state, S.rec.dev);
+            hipLaunchKernelGGL(k_r1cs_det_init, r1cs_blocks(L.n_pairs), dim3(256), 0, st, L, n_wires, d_seed, S.d_cnt, S.d_cnt + M);
+            hipLaunchKernelGGL(k_r1cs_det_first, r1cs_capped(M), dim3(256), 0, st, S.d_cnt, M, S.d_cand, S.d_state, S.rec.dev);
         }
         K16_HIP(ctx, hipGetLastError());
     }
+    return K16_OK;
+}
+
+// The rounds behind r1cs_det_seed, one host synchronise each.  derive(c0, c1, f0) enqueues what judges the candidates
+// cand[c0 .. c1) of a round and appends the wires they give to front[f0 ..); the expansion follows it here.
+template <class Derive>
+static int r1cs_det_rounds(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, Derive&& derive)
+{
+    const ScanDet&   S     = *r->scans->det;
+    const IncList    L     = r1cs_inc_list(r);
+    const size_t     words = r->scans->pairs.present.size();
+    const uint32_t   M = r->M, n_wires = r->n_wires;
+    hipStream_t      st = ctx->stream;
+    unsigned long long* d_known = S.d_masks + words;
+    uint32_t *          d_cnt = S.d_cnt, *d_xr = S.d_cnt + M, *d_round = S.d_by + n_wires;
+    *n_rounds   = 0;
     K16_HIP(ctx, hipStreamSynchronize(st));
     // round k judges the candidates [c0, c1) and derives the frontier [f0, f1)
     uint32_t c0 = 0, c1 = S.rec->n_cand, f0 = 0, round = 0;
@@ -683,15 +887,12 @@ static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t*
             return K16_ERR_HIP;
         }
         round++;
-        {
-            k16_stat_scope sc(ctx, "r1cs_det_derive", st);
-            hipLaunchKernelGGL(k_r1cs_det_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, r->d_mask, d_known,
-                               d_cnt, d_xr, n_wires, d_by, S.d_front, S.d_state);
-        }
+        const int rc = derive(c0, c1, f0);
+        if (rc) return rc;
         {
             // a candidate derives one wire at the most: the frontier is no longer than the candidates' range
             k16_stat_scope sc(ctx, "r1cs_det_expand", st);
-            hipLaunchKernelGGL(k_r1cs_det_expand, capped(c1 - c0), dim3(256), 0, st, S.d_front, f0, round, S.d_start, L, n_wires,
+            hipLaunchKernelGGL(k_r1cs_det_expand, r1cs_capped(c1 - c0), dim3(256), 0, st, S.d_front, f0, round, S.d_start, L, n_wires,
                                d_known, d_round, d_cnt, d_xr, S.d_cand, S.d_state, S.rec.dev);
         }
         K16_HIP(ctx, hipGetLastError());
@@ -708,9 +909,40 @@ static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t*
         f0 = f1, c0 = c1, c1 = c2;
     }
     *n_rounds = round;
-    K16_HIP(ctx, hipMemcpyAsync(S.h_masks + words, d_known, words * 8, hipMemcpyDeviceToHost, st));
-    if (h_by) K16_HIP(ctx, hipMemcpyAsync(h_by, d_by, (size_t)n_wires * 4, hipMemcpyDeviceToHost, st));
-    if (h_round) K16_HIP(ctx, hipMemcpyAsync(h_round, d_round, (size_t)n_wires * 4, hipMemcpyDeviceToHost, st));
+    return K16_OK;
+}
+
+// `known` into h_masks[words ..); round and by as the device left them (r1cs_masks_closure writes round 0 for the seed) where
+// asked for.  Enqueues only.
+static int r1cs_det_download(k16_ctx* ctx, k16_r1cs* r, uint32_t* h_round, uint32_t* h_by)
+{
+    const ScanDet& S     = *r->scans->det;
+    const size_t   words = r->scans->pairs.present.size();
+    const uint32_t n_wires = r->n_wires;
+    hipStream_t    st = ctx->stream;
+    K16_HIP(ctx, hipMemcpyAsync(S.h_masks + words, S.d_masks + words, words * 8, hipMemcpyDeviceToHost, st));
+    if (h_by) K16_HIP(ctx, hipMemcpyAsync(h_by, S.d_by, (size_t)n_wires * 4, hipMemcpyDeviceToHost, st));
+    if (h_round) K16_HIP(ctx, hipMemcpyAsync(h_round, S.d_by + n_wires, (size_t)n_wires * 4, hipMemcpyDeviceToHost, st));
+    return K16_OK;
+}
+
+// h_masks[0 .. words) holds the seed.  Leaves `known` in h_masks[words ..).
+static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by)
+{
+    const ScanDet& S     = *r->scans->det;
+    const IncList  L     = r1cs_inc_list(r);
+    const size_t   words = r->scans->pairs.present.size();
+    hipStream_t    st    = ctx->stream;
+    int            rc    = r1cs_det_seed(ctx, r);
+    if (rc) return rc;
+    rc = r1cs_det_rounds(ctx, r, n_rounds, [&](uint32_t c0, uint32_t c1, uint32_t) {
+        k16_stat_scope sc(ctx, "r1cs_det_derive", st);
+        hipLaunchKernelGGL(k_r1cs_det_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, r->d_mask,
+                           S.d_masks + words, S.d_cnt, S.d_cnt + r->M, r->n_wires, S.d_by, S.d_front, S.d_state);
+        return K16_OK;
+    });
+    if (rc) return rc;
+    if ((rc = r1cs_det_download(ctx, r, h_round, h_by))) return rc;
     K16_HIP(ctx, hipStreamSynchronize(st));
     return K16_OK;
 }
@@ -739,6 +971,149 @@ extern "C" int k16_r1cs_determined_wires(k16_r1cs* r, const uint32_t* h_seed, ui
     }
     const uint64_t* present = r->scans->pairs.present.data();
     r1cs_masks_closure(r->n_wires, present, S.h_masks, S.h_masks + words, n_derived, n_absent, n_open, h_wires, cap, h_status, h_round);
+    return K16_OK;
+    });
+}
+
+// ---- the witness completion
+// the row view on the device, the candidates' value slots and the closing pass's masks
+static int r1cs_solve_alloc(k16_ctx* ctx, k16_r1cs* r, ScanSolve& S)
+{
+    R1csPlan plan; // the layout d_coef was uploaded by (see r1cs_pairs_get)
+    R1csRows rows;
+    if (r1cs_plan_build(r->file, &plan) || plan.plan.n_entries != r->n_entries || r1cs_rows_build(r->file, plan, &rows)) {
+        ctx->err = "r1cs: the row view cannot be built (2^32 terms or more, or another plan than the coefficients')";
+        return K16_ERR_ARG;
+    }
+    const size_t words = r->n_words;
+    int          rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_rowstart, rows.row_start.size() * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_term, rows.term.size() * sizeof(R1csRowRef)))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_val, (size_t)r->M * 32))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_close, (2 * words + 2) * 8))) return rc;
+    K16_HIP(ctx, S.h_close.alloc((2 * words + 2) * 8));
+    hipStream_t st = ctx->stream;
+    K16_HIP(ctx, hipMemcpyAsync(S.d_rowstart, rows.row_start.data(), rows.row_start.size() * 4, hipMemcpyHostToDevice, st));
+    if (!rows.term.empty())
+        K16_HIP(ctx, hipMemcpyAsync(S.d_term, rows.term.data(), rows.term.size() * sizeof(R1csRowRef), hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipStreamSynchronize(st)); // (rows is a local)
+    return K16_OK;
+}
+
+// h_masks[0 .. words) of the closure's stage holds the givens.  K16_ERR_FORMAT before any round when a given value is refused;
+// else leaves the completed assignment in d_wtns and h_wtns, its check in d_rows / d_mask, `known` in h_masks[words ..), and
+// judged | open in h_close.
+static int r1cs_solve_run(k16_ctx* ctx, k16_r1cs* r, void* h_wtns, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by)
+{
+    const ScanDet&   S     = *r->scans->det;
+    const ScanSolve& V     = *r->scans->solve;
+    const IncList    L     = r1cs_inc_list(r);
+    const RowView    rows  = {V.d_rowstart, V.d_term};
+    const size_t     words = r->scans->pairs.present.size(), cw = r->n_words;
+    const uint32_t   M = r->M, n_wires = r->n_wires;
+    hipStream_t      st = ctx->stream;
+    unsigned long long* d_flags = V.d_close + 2 * cw;
+    int                 rc;
+    V.h_close[2 * cw] = V.h_close[2 * cw + 1] = ~0ull;
+    K16_HIP(ctx, hipMemcpyAsync(r->d_wtns, h_wtns, (size_t)n_wires * 32, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemsetAsync(d_flags, 0, 8, st));
+    if ((rc = r1cs_det_seed(ctx, r))) return rc;
+    {
+        k16_stat_scope sc(ctx, "r1cs_solve_mask", st);
+        hipLaunchKernelGGL(k_r1cs_solve_mask, r1cs_blocks(n_wires), dim3(256), 0, st, (uint4*)r->d_wtns.p, n_wires, S.d_masks, d_flags);
+    }
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(V.h_close + 2 * cw, d_flags, 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    if (const unsigned long long flags = V.h_close[2 * cw]) {
+        ctx->err = (flags & WTNS_NOT_BELOW_R) ? "witness: a given wire's value is not below r" : "witness: wire 0 is not 1";
+        return K16_ERR_FORMAT;
+    }
+    rc = r1cs_det_rounds(ctx, r, n_rounds, [&](uint32_t c0, uint32_t c1, uint32_t f0) {
+        {
+            k16_stat_scope sc(ctx, "r1cs_solve_derive", st);
+            hipLaunchKernelGGL(k_r1cs_solve_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, rows, r->d_wtns,
+                               S.d_masks + words, S.d_cnt, S.d_cnt + M, n_wires, S.d_by, V.d_val, S.d_front, S.d_state);
+        }
+        k16_stat_scope sc(ctx, "r1cs_solve_commit", st);
+        hipLaunchKernelGGL(k_r1cs_solve_commit, r1cs_capped(c1 - c0), dim3(256), 0, st, S.d_front, f0, S.d_state, S.d_by, V.d_val,
+                           n_wires, M, r->d_wtns);
+        return K16_OK;
+    });
+    if (rc) return rc;
+    // the closing pass: the check's own kernels on the completed assignment, then the open constraints' verdicts taken out
+    if ((rc = k16_r1cs_launch(r, st, r->d_wtns))) return rc;
+    if (M) {
+        if (!L.n_pairs) K16_HIP(ctx, hipMemsetAsync(S.d_cnt, 0, (size_t)M * 4, st)); // (r1cs_det_seed had nothing to count)
+        k16_stat_scope sc(ctx, "r1cs_solve_close", st);
+        hipLaunchKernelGGL(k_r1cs_solve_close, r1cs_blocks(M), dim3(256), 0, st, r->d_mask, S.d_cnt, M, r->n_words, V.d_close, V.d_close + cw);
+    }
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(V.d_close + 2 * cw + 1, r->d_mask + cw, 8, hipMemcpyDeviceToDevice, st));
+    K16_HIP(ctx, hipMemcpyAsync(V.h_close, V.d_close, (2 * cw + 2) * 8, hipMemcpyDeviceToHost, st));
+    if ((rc = r1cs_det_download(ctx, r, h_round, h_by))) return rc;
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    if (V.h_close[2 * cw + 1]) { // every value on the device is canonical by now and wire 0 was found to be 1
+        ctx->err = "witness completion: the closing check refused the completed assignment";
+        return K16_ERR_HIP;
+    }
+    K16_HIP(ctx, hipMemcpyAsync(h_wtns, r->d_wtns, (size_t)n_wires * 32, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns, const uint32_t* h_given, uint32_t n_given, uint64_t* n_solved,
+                                         uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint64_t* n_failed, uint32_t* h_failed,
+                                         uint32_t cap_failed, uint64_t* n_open_constraints, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
+                                         uint32_t* h_round, uint32_t* h_by)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !h_wtns || !n_solved || !n_absent || !n_open || !n_rounds || !n_failed || !n_open_constraints || (!h_given && n_given))
+        return K16_ERR_ARG;
+    *n_solved = *n_absent = *n_open = *n_failed = *n_open_constraints = 0;
+    *n_rounds                                                        = 0;
+    k16_ctx* ctx                                                     = r->ctx;
+    if (r->forked_on) {
+        ctx->err = "witness completion: a prove call is running on the object";
+        return K16_ERR_ARG;
+    }
+    r->have_values = false; // from here on the sums are this call's, or nobody's: an error leaves no completed check
+    // the givens are looked at before anything is built or launched
+    if (!h_given && (uint64_t)r->file.n_pub_out + 1 + r->file.n_pub_in + r->file.n_prv_in > r->n_wires) {
+        ctx->err = "the header's input wires reach beyond nWires";
+        return K16_ERR_ARG;
+    }
+    for (uint32_t k = 0; h_given && k < n_given; k++) {
+        if (h_given[k] >= r->n_wires) {
+            ctx->err = "given wire number out of range";
+            return K16_ERR_ARG;
+        }
+    }
+    int rc = r1cs_scan_list(ctx, r);
+    if (rc) return rc;
+    if ((rc = r1cs_scan_stage(ctx, r->scans->det, [&](ScanDet& S) { return r1cs_det_alloc(ctx, r, S); }))) return rc;
+    if ((rc = r1cs_scan_stage(ctx, r->scans->solve, [&](ScanSolve& S) { return r1cs_solve_alloc(ctx, r, S); }))) return rc;
+    const ScanDet&   S     = *r->scans->det;
+    const ScanSolve& V     = *r->scans->solve;
+    const size_t     words = r->scans->pairs.present.size(), cw = r->n_words;
+    if (const char* why = r1cs_seed_mask(r->n_wires, r->file.n_pub_out, r->file.n_pub_in, r->file.n_prv_in, h_given, n_given, S.h_masks)) {
+        ctx->err = why;
+        return K16_ERR_ARG;
+    }
+    if ((rc = r1cs_scan_drained(ctx, r1cs_solve_run(ctx, r, h_wtns, n_rounds, h_round, h_by)))) {
+        *n_rounds = 0;
+        return rc;
+    }
+    r->have_values = true;
+    r1cs_masks_closure(r->n_wires, r->scans->pairs.present.data(), S.h_masks, S.h_masks + words, n_solved, n_absent, n_open, h_wires, cap,
+                       h_status, h_round);
+    uint64_t failed = 0, open = 0;
+    for (size_t w = 0; w < cw; w++) {
+        open += (uint64_t)__builtin_popcountll(V.h_close[cw + w]);
+        for (unsigned long long m = V.h_close[w]; m; m &= m - 1, failed++)
+            if (h_failed && failed < cap_failed) h_failed[failed] = (uint32_t)(w * 64u) + (uint32_t)__builtin_ctzll(m);
+    }
+    *n_failed = failed, *n_open_constraints = open;
     return K16_OK;
     });
 }
