@@ -724,6 +724,52 @@ int  k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns /* n_wires x 32 B stand
                                uint32_t* h_wires /* lowest min(*n_open, cap) OPEN wires, ascending */, uint32_t cap, uint8_t* h_status,
                                uint32_t* h_round, uint32_t* h_by);
 
+/* ---- witness completion, second rule: the bit decompositions the booleans force ----
+ * The linear rule stops at a constraint with two unknown wires.  The commonest such constraint of a circom circuit is
+ * Num2Bits: ONE linear constraint sum 2^i b_i = x over wires that each carry their own b (b - 1) = 0.
+ * BOOLEAN: a wire x >= 1 is BOOLEAN when some constraint has a non-zero merged coefficient on no wire other than x and wire 0
+ * and, with wire 0 = 1 and A = a1 x + a0, B = b1 x + b0, C = c1 x + c0, its residual quad x^2 + lin x + k has quad = a1 b1 != 0,
+ * k = a0 b0 - c0 = 0 and lin + quad = 0 (lin = a1 b0 + a0 b1 - c1): the roots are exactly 0 and 1.  A function of the circuit
+ * alone; b (b - 1) = 0, b (1 - b) = 0, b b = b and their scaled forms qualify.
+ *   k16_r1cs_boolean_wires   *n_boolean = how many wires are BOOLEAN; h_mark (may be NULL): n_wires bytes, 1 for a BOOLEAN wire.
+ *                            Needs no completed check; the marks are made by the first call that needs them and stay with the
+ *                            object.  THREADING and errors as k16_r1cs_incidences.
+ * THE BIT RULE, with respect to a set K of known wires: constraint c has k unknown wires x_1 .. x_k (merged coefficient
+ * non-zero, outside K), 2 <= k <= 253; a0, b0, c0 are the sums of its combinations over its wires in K.  The rule applies when
+ *   (a) every x_j is BOOLEAN;
+ *   (b) every unknown has A^ = 0, or every unknown has B^ = 0: the residual is sum lin_j x_j + k0 with
+ *       lin_j = A^_j b0 + B^_j a0 - C^_j, k0 = a0 b0 - c0;
+ *   (c) there is a lambda != 0 with lin_j / lambda = 2^(e_j) as canonical integers, the e_j pairwise distinct, 0 <= e_j <= 252.
+ *       lambda is tried as the lin of the LOWEST-numbered unknown wire, then as that of the HIGHEST-numbered (a lin of 0 is no
+ *       lambda); where neither serves, c gives nothing.  This is part of the definition.
+ * With v = -k0 / lambda as a canonical integer: v < 2^253 and every set bit of v among the e_j -> c is FEASIBLE and every x_j
+ * joins K with the value bit e_j of v; otherwise c is INFEASIBLE: it gives nothing, its wires stay as they are.
+ * LEVELS: the linear rule runs to its fixed point as in k16_r1cs_complete_witness; then ONE bit level examines every constraint
+ * with respect to that K.  The wires it solves get the next round number, by[x] = the LOWEST feasible c that names x, and the
+ * value is that constraint's; the linear rule resumes.  The call ends when a bit level solves nothing.
+ * SOUND: a satisfying witness that agrees on K has x_j in {0, 1} by the wires' own constraints, and sum 2^(e_j) x_j < 2^253 < r:
+ * distinct 0/1 vectors give distinct residuals, so the solution is unique where it exists -- whichever lambda was found.
+ * *n_infeasible > 0 proves that NO satisfying witness has these givens, exactly as *n_failed > 0 does; *n_open == 0 &&
+ * *n_failed == 0 still means the returned bytes are the only satisfying witness with these givens.
+ *   rules            K16_SOLVE_RULE_LINEAR, or K16_SOLVE_RULE_LINEAR | K16_SOLVE_RULE_BITS; anything else is K16_ERR_ARG (the
+ *                    object keeps the check it had)
+ *   *n_by_bits       required: the wires the bit rule solved
+ *   *n_infeasible    required: the INFEASIBLE constraints of the FINAL state; h_infeasible (may be NULL) the lowest
+ *                    min(*n_infeasible, cap_infeasible) of them, ascending
+ *   h_rule (may be NULL)   n_wires bytes: 0 for a wire that is given or not solved, 1 for the linear rule, 2 for the bit rule
+ * Every other argument, the returned assignment, STATE, errors and THREADING are k16_r1cs_complete_witness's.  With
+ * rules = K16_SOLVE_RULE_LINEAR every output byte is that call's and *n_by_bits = *n_infeasible = 0.  The result is a function
+ * of circuit, givens, values and rules alone: the same bytes on every run.  One host synchronise per bit level on top of the
+ * linear rounds; a constraint-side index of the incidence list (4 bytes an incidence) is uploaded by the first call that asks
+ * for the bit rule (csrc/r1cs_scan.hip, csrc/r1cs_bools.h). */
+enum { K16_SOLVE_RULE_LINEAR = 1, K16_SOLVE_RULE_BITS = 2 };
+int  k16_r1cs_boolean_wires(k16_r1cs* r, uint64_t* n_boolean, uint8_t* h_mark /* n_wires bytes, may be NULL */);
+int  k16_r1cs_complete_witness_ex(k16_r1cs* r, void* h_wtns, const uint32_t* h_given, uint32_t n_given, uint32_t rules,
+                                  uint64_t* n_solved, uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint64_t* n_failed,
+                                  uint32_t* h_failed, uint32_t cap_failed, uint64_t* n_open_constraints, uint32_t* h_wires, uint32_t cap,
+                                  uint8_t* h_status, uint32_t* h_round, uint32_t* h_by, uint64_t* n_by_bits, uint64_t* n_infeasible,
+                                  uint32_t* h_infeasible, uint32_t cap_infeasible, uint8_t* h_rule /* n_wires bytes, may be NULL */);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

@@ -5,6 +5,8 @@
 //   k16_r1cs_second_values     which admit exactly ONE other value, every other wire held fixed?  k_r1cs_kinds, _agree, _shifts (10c)
 //   k16_r1cs_determined_wires  which does the circuit force, given the seed wires?  k_r1cs_det_init, _first, _derive, _expand (10d)
 //   k16_r1cs_complete_witness  which VALUES do the given wires force?  the closure's frontier + k_r1cs_solve_mask, _derive, _commit, _close (10e)
+//   k16_r1cs_complete_witness_ex  ... and which bit decompositions?  k_r1cs_bits_filter, k_r1cs_solve_bits, k_r1cs_bits_commit over the
+//                              boolean marks of k16_r1cs_boolean_wires (r1cs_bools.h) (10f)
 // Each kernel is described where it stands.  The list and every buffer here are made by the first call that needs them: create
 // and check calls allocate and launch nothing of this file.  From masks to counts, lists and status bytes: r1cs_masks.h.
 #include <string.h>
@@ -13,6 +15,7 @@
 #include <vector>
 #include "r1cs_obj.h"
 #include "frinv_dev.h"
+#include "r1cs_bools.h"
 #include "r1cs_masks.h"
 #include "r1cs_pairs.h"
 #include "r1cs_rows.h"
@@ -557,7 +560,251 @@ __global__ void __launch_bounds__(256) k_r1cs_solve_close(const unsigned long lo
     }
 }
 
-// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Four stages, each made whole by the first call
+// The bit rule of the witness completion (k16_r1cs_complete_witness_ex with K16_SOLVE_RULE_BITS).  At
+// the linear rule's fixed point a constraint c with k = 2 .. 253 wires x_1 .. x_k outside K gives all of them when
+//   (a) every x_j is BOOLEAN (r1cs_bools.h: the circuit itself holds it to {0, 1}),
+//   (b) the unknowns with A^ != 0 and those with B^ != 0 are not both there: the residual is linear in them,
+//           sum lin_j x_j + k0,   lin_j = A^_j b0 + B^_j a0 - C^_j,   k0 = a0 b0 - c0     (a0, b0, c0: the sums over K),
+//   (c) with lambda = the lin of the LOWEST unknown wire or, failing that, of the HIGHEST, every lin_j / lambda is 2^(e_j) as a
+//       canonical integer, the e_j distinct and at most 252.
+// Then v = -k0 / lambda (canonical) must be sum 2^(e_j) x_j < 2^253 < r: a sum of distinct powers of two below r determines its
+// bits, so x_j = bit e_j of v where v has no bit outside the e_j (FEASIBLE), and no 0/1 assignment exists otherwise (INFEASIBLE:
+// nothing is given, the constraint's bit is set in `infeasible`).
+//   k_r1cs_bits_filter   a lane per constraint: 2 <= cnt <= 253 -> the bit candidates (their own list, any order)
+//   k_r1cs_solve_bits    a wave per candidate (below)
+//   k_r1cs_bits_commit   a lane per frontier wire: by[x] is final, wtns[x] = the bit the row by[x] claimed
+// THE COMMIT HAZARD again (two rows of a level may claim x with different bits): a wave leaves its claim in a byte of its OWN,
+// claim[i] of the incidence i = (x, c) -- no two waves write one byte -- and the commit finds the incidence (x, by[x]) in x's
+// column, which is ordered by constraint.  by[x] was all ones before the level, so the byte read is this level's.
+// Scalings (see k_r1cs_solve_derive): coefficients k 2^522, sums s 2^261, frmul9 divides by 2^261.
+//   lin_j   frmul9(A^ 2^522, b0 2^261) - C^ 2^522 = lin_j 2^522 (or B^ a0; never both, by (b); neither: -C^ alone)
+//   lambda  frmul9(lambda 2^522, 1) = lambda 2^261, its R' value; frinv9 gives the R' value of the inverse, lambda^-1 2^261 =: I
+//   ratio   frmul9(lin_j 2^522, I) = (lin_j / lambda) 2^522; frmul9(., 1) = (lin_j / lambda) 2^261; fr9_to_standard divides by
+//           2^261 once more and reduces: the canonical integer lin_j / lambda, on which "a single bit" is a popcount
+//   v       k0 2^261 = frmul9(a0 2^261, b0 2^261) - c0 2^261; frmul9(k0 2^261, I) = (k0 / lambda) 2^261, negated by
+//           frsub9(0, .), fr9_to_standard: the canonical v
+// Every operand is < 2r (sums by fradd9 / frsub9, products by frmul9), as in the kernels above.
+constexpr uint32_t BITS_MIN = 2, BITS_MAX = 253; // unknowns of a bit row: exponents 0 .. 252
+constexpr uint32_t BITS_PER_LANE = 4;            // 4 x 64 lanes >= BITS_MAX
+
+// cnt: the outside counts at the fixed point.  total: cleared before the launch.  Launched with whole waves, any grid.
+__global__ void __launch_bounds__(256) k_r1cs_bits_filter(const uint32_t* __restrict__ cnt, uint32_t M, uint32_t* __restrict__ bcand, uint32_t* total)
+{
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < M; base += (uint64_t)gridDim.x * 256u) {
+        const uint64_t c = base + threadIdx.x;
+        wave_append(bcand, total, M, c < M && cnt[c] >= BITS_MIN && cnt[c] <= BITS_MAX, (uint32_t)c);
+    }
+}
+
+// The constraint-side index: cinc[cstart[c] .. cstart[c + 1]) are the incidences (indices into L.inc) of constraint c, by wire.
+struct RowIndex {
+    const uint32_t* __restrict__ cstart;
+    const uint32_t* __restrict__ cinc;
+};
+
+__device__ __forceinline__ Fr9 wave_bcast9(const Fr9& a, int src)
+{
+    Fr9 o;
+#pragma unroll
+    for (int i = 0; i < 9; i++) o.l[i] = (uint32_t)__shfl((int)a.l[i], src, 64);
+    return o;
+}
+
+// bcand[0 .. *n_bcand): the bit candidates of this level; ONE WAVE per workgroup, a workgroup strides the candidates.  Every
+// branch below is taken by the whole wave (its condition comes from a ballot, a broadcast or a reduction), so the shuffles, the
+// barriers and wave_append see all 64 lanes.
+//   1  the unknown incidences are gathered through LDS in the order of the row index (by wire): slot p of the row lies in lane
+//      p % 64, register p / 64 -- the lowest unknown wire in lane 0, up to BITS_PER_LANE a lane
+//   2  tests (a) and (b): they need no arithmetic and end most rows that are no decomposition
+//   3  the three row sums, lanes striding the row, butterfly reduction (unknown wires hold 0 in wtns: the invariant masks them)
+//   4  lin_j; lambda's lane runs frinv9, the inverse is broadcast; ratio_j to canonical standard form, the single-bit test
+//   5  the exponents are ORed over the wave into a 256-bit mask: its popcount is k exactly when they are distinct
+//   6  v and the subset test
+//   7  the claims: claim[i] = the bit, atomicMin(by[x], c), the first claim appends x to the frontier
+__global__ void __launch_bounds__(64) k_r1cs_solve_bits(const uint32_t* __restrict__ bcand, const uint32_t* __restrict__ n_bcand, const IncList L,
+                                                        const RowView V, const RowIndex X, const Fr* __restrict__ wtns,
+                                                        const unsigned long long* __restrict__ known, const unsigned long long* __restrict__ boolean,
+                                                        const uint32_t* __restrict__ cnt, uint32_t n_wires, uint32_t* by, uint8_t* __restrict__ claim,
+                                                        unsigned long long* infeasible, uint32_t* __restrict__ front, DetState* st)
+{
+    __shared__ uint32_t slot[BITS_PER_LANE * 64];
+    const uint32_t      lane = threadIdx.x & 63u;
+    const uint32_t      n    = min(*n_bcand, L.M);
+    for (uint32_t w = blockIdx.x; w < n; w += gridDim.x) {
+        const uint32_t c = bcand[w];
+        if (c >= L.M) continue;
+        const uint32_t k = cnt[c];
+        if (k < BITS_MIN || k > BITS_MAX) continue;
+        // 1: the unknown incidences, in the order of the index
+        const uint32_t cs = X.cstart[c], ce = min(X.cstart[c + 1], L.n_pairs);
+        uint32_t       found = 0;
+        __syncthreads(); // (the slots of the candidate before are read by now)
+        for (uint32_t at = cs; at < ce; at += 64u) {
+            uint32_t idx = DET_NONE;
+            bool     out = false;
+            if (at + lane < ce) {
+                idx = X.cinc[at + lane];
+                if (idx < L.n_pairs) {
+                    const uint32_t x = L.wire[idx];
+                    out              = x < n_wires && L.inc[idx].x == c && !det_bit(known, x);
+                }
+            }
+            const unsigned long long votes = __ballot(out);
+            const uint32_t           pos   = found + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
+            if (out && pos < BITS_PER_LANE * 64u) slot[pos] = idx;
+            found += (uint32_t)__popcll(votes);
+        }
+        __syncthreads();
+        if (found != k) continue; // (cnt counts exactly the incidences outside K)
+        uint32_t idx[BITS_PER_LANE], x[BITS_PER_LANE];
+        uint4    e[BITS_PER_LANE];
+        bool     ok = true, onA = false, onB = false;
+#pragma unroll
+        for (uint32_t j = 0; j < BITS_PER_LANE; j++) {
+            const uint32_t p = lane + 64u * j;
+            idx[j]           = p < k ? slot[p] : DET_NONE;
+            x[j]             = 0;
+            e[j]             = make_uint4(0, R1CS_PAIR_NONE, R1CS_PAIR_NONE, R1CS_PAIR_NONE);
+            if (p < k) {
+                x[j] = L.wire[idx[j]];
+                e[j] = L.inc[idx[j]];
+                ok   = ok && det_bit(boolean, x[j]);          // (a)
+                onA  = onA || e[j].y != R1CS_PAIR_NONE;
+                onB  = onB || e[j].z != R1CS_PAIR_NONE;
+            }
+        }
+        // 2: (a), and (b): unknowns on A and unknowns on B (one wire on both included) leave a product of unknowns
+        if (__ballot(!ok) || (__ballot(onA) && __ballot(onB))) continue;
+        // 3: the row sums, in every lane
+        Fr9 sum[3];
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            const uint32_t ls = V.start[(size_t)m * L.M + c], le = V.start[(size_t)m * L.M + c + 1];
+            Fr9            acc = fq9_zero();
+            for (uint64_t t = (uint64_t)ls + lane; t < le; t += 64u) acc = fradd9(acc, solve_term(V, L, wtns, n_wires, (uint32_t)t));
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                Fr9 o;
+#pragma unroll
+                for (int i = 0; i < 9; i++) o.l[i] = (uint32_t)__shfl_xor((int)acc.l[i], d, 64);
+                acc = fradd9(acc, o);
+            }
+            sum[m] = wave_bcast9(acc, 0); // one representative of the sum for the whole wave
+        }
+        // 4: lin_j 2^522
+        Fr9 one  = fq9_zero();
+        one.l[0] = 1;
+        Fr9 lin[BITS_PER_LANE];
+#pragma unroll
+        for (uint32_t j = 0; j < BITS_PER_LANE; j++) {
+            lin[j] = fq9_zero();
+            if (e[j].y != R1CS_PAIR_NONE) lin[j] = frmul9(L.at(e[j].y), sum[1]);
+            else if (e[j].z != R1CS_PAIR_NONE) lin[j] = frmul9(L.at(e[j].z), sum[0]);
+            if (e[j].w != R1CS_PAIR_NONE) lin[j] = frsub9(lin[j], L.at(e[j].w));
+        }
+        const Fr9 k0 = frsub9(frmul9(sum[0], sum[1]), sum[2]);
+        // lambda: the lin of slot 0 (the lowest unknown wire), then of slot k - 1 (the highest)
+        bool     solved = false;
+        Fr9      inv    = fq9_zero();
+        uint32_t ex[BITS_PER_LANE] = {0, 0, 0, 0};
+        uint32_t mask[8];
+        for (uint32_t attempt = 0; attempt < 2 && !solved; attempt++) {
+            const uint32_t p = attempt == 0 ? 0u : k - 1u, src = p & 63u, reg = p >> 6;
+            Fr9            lam = lin[0];
+#pragma unroll
+            for (uint32_t j = 1; j < BITS_PER_LANE; j++)
+                if (reg == j) lam = lin[j];
+            lam = wave_bcast9(lam, (int)src);
+            if (!fr9_nonzero(lam)) continue; // (the same value in every lane)
+            if (lane == src) inv = frinv9(frmul9(lam, one));
+            inv = wave_bcast9(inv, (int)src);
+            bool fits = true;
+#pragma unroll
+            for (int i = 0; i < 8; i++) mask[i] = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < BITS_PER_LANE; j++) {
+                if (lane + 64u * j >= k) continue;
+                const Fr ratio = fr9_to_standard(frmul9(frmul9(lin[j], inv), one));
+                uint32_t pop = 0, at = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    pop += (uint32_t)__popc(ratio.v[i]);
+                    if (ratio.v[i]) at = 32u * i + (uint32_t)__ffs((int)ratio.v[i]) - 1u;
+                }
+                if (pop != 1u || at >= BITS_MAX) {
+                    fits = false;
+                    continue;
+                }
+                ex[j] = at;
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    if ((at >> 5) == (uint32_t)i) mask[i] |= 1u << (at & 31u);
+            }
+            if (__ballot(!fits)) continue;
+            // 5: distinct exponents
+            uint32_t pop = 0;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) mask[i] |= (uint32_t)__shfl_xor((int)mask[i], d, 64);
+                pop += (uint32_t)__popc(mask[i]);
+            }
+            solved = pop == k;
+        }
+        if (!solved) continue;
+        // 6: v = -k0 / lambda, canonical; FEASIBLE when it has no bit outside the exponents (then v < 2^253 as well)
+        const Fr v       = fr9_to_standard(frsub9(fq9_zero(), frmul9(k0, inv)));
+        uint32_t outside = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) outside |= v.v[i] & ~mask[i];
+        if (outside) {
+            if (lane == 0) atomicOr(&infeasible[c >> 6], 1ull << (c & 63u));
+            continue;
+        }
+        // 7: the claims
+#pragma unroll
+        for (uint32_t j = 0; j < BITS_PER_LANE; j++) {
+            bool add = false;
+            if (lane + 64u * j < k) {
+                uint32_t word = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    if ((ex[j] >> 5) == (uint32_t)i) word = v.v[i];
+                claim[idx[j]] = (uint8_t)((word >> (ex[j] & 31u)) & 1u);
+                add           = atomicMin(&by[x[j]], c) == DET_NONE;
+            }
+            wave_append(front, &st->n_front, n_wires, add, x[j]);
+        }
+    }
+}
+
+// front[from .. st->n_front): the wires this bit level solved; by is final for them (k_r1cs_solve_bits has ended).  The incidence
+// (x, by[x]) is found by bisection in x's column (start: the closure's column starts) and its claim goes into wtns.  A workgroup
+// strides the wires: any grid covers them.
+__global__ void __launch_bounds__(256) k_r1cs_bits_commit(const uint32_t* __restrict__ front, uint32_t from, const DetState* st,
+                                                          const uint32_t* __restrict__ by, const uint32_t* __restrict__ start, const IncList L,
+                                                          const uint8_t* __restrict__ claim, uint32_t n_wires, uint4* __restrict__ wtns)
+{
+    const uint32_t total = __atomic_load_n(&st->n_front, __ATOMIC_RELAXED);
+    const uint32_t todo  = total > from ? total - from : 0;
+    for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < todo; k += (uint64_t)gridDim.x * 256u) {
+        const uint32_t x = front[from + k];
+        if (x >= n_wires) continue;
+        const uint32_t c  = by[x];
+        uint32_t       lo = start[x], hi = min(start[x + 1], L.n_pairs);
+        while (lo < hi) { // the first incidence of the column whose constraint is not below c
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (L.inc[mid].x < c) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < min(start[x + 1], L.n_pairs) && L.inc[lo].x == c) {
+            wtns[2 * (size_t)x]     = make_uint4(claim[lo], 0, 0, 0);
+            wtns[2 * (size_t)x + 1] = make_uint4(0, 0, 0, 0);
+        }
+    }
+}
+
+// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Six stages, each made whole by the first call
 // that needs it and kept until the object goes; a stage is ready when its pointer is set.
 struct ScanList { // the list on the device, and the unbound-wire scan's mask
     DevBuf<uint4>                 inc;     // R1csPair of every incidence of the wires 1 .. n_wires - 1
@@ -584,6 +831,18 @@ struct ScanDet { // the determinism closure
     DevBuf<DetState>              d_state;
     PinnedBuf<DetRecord>          rec;     // pinned, device-mapped
 };
+struct ScanBool { // the boolean marks: a function of the circuit alone
+    R1csBools                  host;
+    DevBuf<unsigned long long> d_mark; // [ceil(n_wires / 64)]
+};
+struct ScanBits { // the bit rule of the witness completion: on top of the completion's stage
+    DevBuf<uint32_t>              d_cstart;     // [M + 1] the constraint-side index over the device list
+    DevBuf<uint32_t>              d_cinc;       // [n_pairs]
+    DevBuf<uint8_t>               d_claim;      // [n_pairs] the bit a row claimed for the wire of its incidence
+    DevBuf<uint32_t>              d_bcand;      // [M] the bit candidates of a level | [1] their number
+    DevBuf<unsigned long long>    d_infeasible; // [n_words] the infeasible rows of the last level
+    PinnedBuf<unsigned long long> h_infeasible;
+};
 struct ScanSolve { // the witness completion: on top of the closure's stage
     DevBuf<uint32_t>              d_rowstart; // [3 M + 1] the row view
     DevBuf<uint2>                 d_term;     // [n_terms]
@@ -600,6 +859,8 @@ struct k16::R1csScans {
     std::unique_ptr<ScanSecond> second;
     std::unique_ptr<ScanDet>    det;
     std::unique_ptr<ScanSolve>  solve;
+    std::unique_ptr<ScanBool>   boolean;
+    std::unique_ptr<ScanBits>   bits;
 };
 void k16::r1cs_scans_delete(R1csScans* s) { delete s; }
 
@@ -631,7 +892,7 @@ static int r1cs_scan_alloc(k16_ctx* ctx, DevBuf<T>& b, size_t bytes)
 {
     const hipError_t e = b.alloc(std::max<size_t>(bytes, 32));
     if (e == hipSuccess) return K16_OK;
-    ctx->err = std::string("unbound-wire scan: hipMalloc: ") + hipGetErrorString(e);
+    ctx->err = std::string("r1cs diagnostics: hipMalloc: ") + hipGetErrorString(e);
     (void)hipGetLastError();
     return e == hipErrorOutOfMemory ? K16_ERR_NOMEM : K16_ERR_HIP;
 }
@@ -864,10 +1125,16 @@ static int r1cs_det_seed(k16_ctx* ctx, k16_r1cs* r)
     return K16_OK;
 }
 
+// Where the rounds stand: cand[0 .. c0) are judged, front[0 .. f0) expanded, `round` levels taken.  A fresh cursor starts behind
+// r1cs_det_seed; the witness completion's bit levels move f0 and round on between two runs of the rounds.
+struct DetCursor {
+    uint32_t c0 = 0, f0 = 0, round = 0;
+};
+
 // The rounds behind r1cs_det_seed, one host synchronise each.  derive(c0, c1, f0) enqueues what judges the candidates
 // cand[c0 .. c1) of a round and appends the wires they give to front[f0 ..); the expansion follows it here.
 template <class Derive>
-static int r1cs_det_rounds(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, Derive&& derive)
+static int r1cs_det_rounds(k16_ctx* ctx, k16_r1cs* r, DetCursor* cur, Derive&& derive)
 {
     const ScanDet&   S     = *r->scans->det;
     const IncList    L     = r1cs_inc_list(r);
@@ -876,10 +1143,9 @@ static int r1cs_det_rounds(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, Derive
     hipStream_t      st = ctx->stream;
     unsigned long long* d_known = S.d_masks + words;
     uint32_t *          d_cnt = S.d_cnt, *d_xr = S.d_cnt + M, *d_round = S.d_by + n_wires;
-    *n_rounds   = 0;
     K16_HIP(ctx, hipStreamSynchronize(st));
     // round k judges the candidates [c0, c1) and derives the frontier [f0, f1)
-    uint32_t c0 = 0, c1 = S.rec->n_cand, f0 = 0, round = 0;
+    uint32_t c0 = cur->c0, c1 = S.rec->n_cand, f0 = cur->f0, round = cur->round;
     while (c1 > c0) {
         // every round that goes on adds a wire, and wire 0 is never added: at most n_wires - 1 rounds
         if (round + 1 >= n_wires || c1 > M) {
@@ -908,7 +1174,7 @@ static int r1cs_det_rounds(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, Derive
         }
         f0 = f1, c0 = c1, c1 = c2;
     }
-    *n_rounds = round;
+    cur->c0 = c1, cur->f0 = f0, cur->round = round; // every candidate listed so far is judged
     return K16_OK;
 }
 
@@ -935,13 +1201,16 @@ static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t*
     hipStream_t    st    = ctx->stream;
     int            rc    = r1cs_det_seed(ctx, r);
     if (rc) return rc;
-    rc = r1cs_det_rounds(ctx, r, n_rounds, [&](uint32_t c0, uint32_t c1, uint32_t) {
+    DetCursor cur;
+    *n_rounds = 0;
+    rc        = r1cs_det_rounds(ctx, r, &cur, [&](uint32_t c0, uint32_t c1, uint32_t) {
         k16_stat_scope sc(ctx, "r1cs_det_derive", st);
         hipLaunchKernelGGL(k_r1cs_det_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, r->d_mask,
                            S.d_masks + words, S.d_cnt, S.d_cnt + r->M, r->n_wires, S.d_by, S.d_front, S.d_state);
         return K16_OK;
     });
     if (rc) return rc;
+    *n_rounds = cur.round;
     if ((rc = r1cs_det_download(ctx, r, h_round, h_by))) return rc;
     K16_HIP(ctx, hipStreamSynchronize(st));
     return K16_OK;
@@ -1000,10 +1269,81 @@ static int r1cs_solve_alloc(k16_ctx* ctx, k16_r1cs* r, ScanSolve& S)
     return K16_OK;
 }
 
+// the boolean marks, on the host and on the device
+static int r1cs_bool_make(k16_ctx* ctx, k16_r1cs* r, ScanBool& S)
+{
+    r1cs_bools_build(r->file, &S.host);
+    const size_t words = S.host.mark.size();
+    const int    rc    = r1cs_scan_alloc(ctx, S.d_mark, words * 8);
+    if (rc) return rc;
+    if (words) K16_HIP(ctx, hipMemcpyAsync(S.d_mark, S.host.mark.data(), words * 8, hipMemcpyHostToDevice, ctx->stream));
+    K16_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return K16_OK;
+}
+static int r1cs_bool_stage(k16_ctx* ctx, k16_r1cs* r)
+{
+    const int rc = r1cs_pairs_get(ctx, r); // (the owner of every stage)
+    if (rc) return rc;
+    K16_HIP(ctx, hipSetDevice(ctx->device));
+    return r1cs_scan_stage(ctx, r->scans->boolean, [&](ScanBool& S) { return r1cs_bool_make(ctx, r, S); });
+}
+
+extern "C" int k16_r1cs_boolean_wires(k16_r1cs* r, uint64_t* n_boolean, uint8_t* h_mark)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_boolean) return K16_ERR_ARG;
+    *n_boolean   = 0;
+    const int rc = r1cs_bool_stage(r->ctx, r);
+    if (rc) return rc;
+    const R1csBools& B = r->scans->boolean->host;
+    *n_boolean         = B.n;
+    for (uint32_t i = 0; h_mark && i < r->n_wires; i++) h_mark[i] = (uint8_t)((B.mark[i >> 6] >> (i & 63u)) & 1u);
+    return K16_OK;
+    });
+}
+
+// the constraint-side index over the device list (a counting sort keeps the list's order: by wire), the claims, the bit
+// candidates and the infeasible rows
+static int r1cs_bits_alloc(k16_ctx* ctx, k16_r1cs* r, ScanBits& S)
+{
+    const R1csPairs&      P    = r->scans->pairs;
+    const size_t          skip = P.start[1], n = r1cs_walked(P), M = r->M, words = r->n_words;
+    std::vector<uint32_t> cstart(M + 1, 0), cinc(n);
+    for (size_t i = 0; i < n; i++)
+        if (P.pair[skip + i].constraint < M) cstart[P.pair[skip + i].constraint + 1]++;
+    for (size_t c = 0; c < M; c++) cstart[c + 1] += cstart[c];
+    {
+        std::vector<uint32_t> cur(cstart.begin(), cstart.end() - 1);
+        for (size_t i = 0; i < n; i++)
+            if (P.pair[skip + i].constraint < M) cinc[cur[P.pair[skip + i].constraint]++] = (uint32_t)i;
+    }
+    int rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_cstart, (M + 1) * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_cinc, n * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_claim, n))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_bcand, (M + 1) * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_infeasible, words * 8))) return rc;
+    K16_HIP(ctx, S.h_infeasible.alloc(std::max<size_t>(words * 8, 8)));
+    hipStream_t st = ctx->stream;
+    K16_HIP(ctx, hipMemcpyAsync(S.d_cstart, cstart.data(), (M + 1) * 4, hipMemcpyHostToDevice, st));
+    if (n) K16_HIP(ctx, hipMemcpyAsync(S.d_cinc, cinc.data(), n * 4, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipMemsetAsync(S.d_claim, 0, std::max<size_t>(n, 1), st));
+    K16_HIP(ctx, hipStreamSynchronize(st)); // (cstart and cinc are locals)
+    return K16_OK;
+}
+
+// what the bit levels of a run did, for the host's maps
+struct BitsRun {
+    uint64_t              n_by_bits = 0;
+    std::vector<uint32_t> rounds; // the rounds that were bit levels, ascending
+};
+constexpr uint32_t BITS_GRID = 2048; // workgroups (of one wave) of k_r1cs_solve_bits
+
 // h_masks[0 .. words) of the closure's stage holds the givens.  K16_ERR_FORMAT before any round when a given value is refused;
 // else leaves the completed assignment in d_wtns and h_wtns, its check in d_rows / d_mask, `known` in h_masks[words ..), and
-// judged | open in h_close.
-static int r1cs_solve_run(k16_ctx* ctx, k16_r1cs* r, void* h_wtns, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by)
+// judged | open in h_close.  bits: null for the linear rule alone; else the bit levels are taken and the infeasible rows of the
+// final state lie in the bit stage's h_infeasible.
+static int r1cs_solve_run(k16_ctx* ctx, k16_r1cs* r, void* h_wtns, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by, BitsRun* bits)
 {
     const ScanDet&   S     = *r->scans->det;
     const ScanSolve& V     = *r->scans->solve;
@@ -1029,18 +1369,58 @@ static int r1cs_solve_run(k16_ctx* ctx, k16_r1cs* r, void* h_wtns, uint32_t* n_r
         ctx->err = (flags & WTNS_NOT_BELOW_R) ? "witness: a given wire's value is not below r" : "witness: wire 0 is not 1";
         return K16_ERR_FORMAT;
     }
-    rc = r1cs_det_rounds(ctx, r, n_rounds, [&](uint32_t c0, uint32_t c1, uint32_t f0) {
+    DetCursor cur;
+    *n_rounds = 0;
+    // for the run that takes no bit level at all (no constraints, no incidences): the mask is downloaded whatever happened.
+    // Every level clears it again, so that what is reported is the last level's
+    if (bits) K16_HIP(ctx, hipMemsetAsync(r->scans->bits->d_infeasible, 0, std::max<size_t>(cw * 8, 8), st));
+    for (;;) {
+        // the linear rule to its fixed point
+        rc = r1cs_det_rounds(ctx, r, &cur, [&](uint32_t c0, uint32_t c1, uint32_t f0) {
+            {
+                k16_stat_scope sc(ctx, "r1cs_solve_derive", st);
+                hipLaunchKernelGGL(k_r1cs_solve_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, rows, r->d_wtns,
+                                   S.d_masks + words, S.d_cnt, S.d_cnt + M, n_wires, S.d_by, V.d_val, S.d_front, S.d_state);
+            }
+            k16_stat_scope sc(ctx, "r1cs_solve_commit", st);
+            hipLaunchKernelGGL(k_r1cs_solve_commit, r1cs_capped(c1 - c0), dim3(256), 0, st, S.d_front, f0, S.d_state, S.d_by, V.d_val,
+                               n_wires, M, r->d_wtns);
+            return K16_OK;
+        });
+        if (rc) return rc;
+        // ONE bit level on that state: it is the next round where it solves a wire, and the call's end where it does not
+        if (!bits || !M || !L.n_pairs || cur.round + 1 >= n_wires) break;
+        const ScanBits& B       = *r->scans->bits;
+        uint32_t*       d_total = B.d_bcand + M;
+        K16_HIP(ctx, hipMemsetAsync(d_total, 0, 4, st));
+        K16_HIP(ctx, hipMemsetAsync(B.d_infeasible, 0, cw * 8, st)); // what is reported is the LAST level's: the final state's
         {
-            k16_stat_scope sc(ctx, "r1cs_solve_derive", st);
-            hipLaunchKernelGGL(k_r1cs_solve_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, rows, r->d_wtns,
-                               S.d_masks + words, S.d_cnt, S.d_cnt + M, n_wires, S.d_by, V.d_val, S.d_front, S.d_state);
+            k16_stat_scope sc(ctx, "r1cs_solve_bits", st);
+            hipLaunchKernelGGL(k_r1cs_bits_filter, r1cs_capped(M), dim3(256), 0, st, S.d_cnt, M, B.d_bcand, d_total);
+            hipLaunchKernelGGL(k_r1cs_solve_bits, dim3(std::min(M, BITS_GRID)), dim3(64), 0, st, B.d_bcand, d_total, L, rows,
+                               RowIndex{B.d_cstart, B.d_cinc}, r->d_wtns, S.d_masks + words, r->scans->boolean->d_mark, S.d_cnt, n_wires, S.d_by,
+                               B.d_claim, B.d_infeasible, S.d_front, S.d_state);
+            hipLaunchKernelGGL(k_r1cs_bits_commit, r1cs_capped(n_wires), dim3(256), 0, st, S.d_front, cur.f0, S.d_state, S.d_by, S.d_start, L,
+                               B.d_claim, n_wires, (uint4*)r->d_wtns.p);
         }
-        k16_stat_scope sc(ctx, "r1cs_solve_commit", st);
-        hipLaunchKernelGGL(k_r1cs_solve_commit, r1cs_capped(c1 - c0), dim3(256), 0, st, S.d_front, f0, S.d_state, S.d_by, V.d_val,
-                           n_wires, M, r->d_wtns);
-        return K16_OK;
-    });
-    if (rc) return rc;
+        {
+            k16_stat_scope sc(ctx, "r1cs_det_expand", st);
+            hipLaunchKernelGGL(k_r1cs_det_expand, r1cs_capped(n_wires), dim3(256), 0, st, S.d_front, cur.f0, cur.round + 1, S.d_start, L, n_wires,
+                               S.d_masks + words, S.d_by + n_wires, S.d_cnt, S.d_cnt + M, S.d_cand, S.d_state, S.rec.dev);
+        }
+        K16_HIP(ctx, hipGetLastError());
+        K16_HIP(ctx, hipStreamSynchronize(st));
+        const uint32_t f1 = S.rec->n_front;
+        if (f1 < cur.f0 || f1 > n_wires) {
+            ctx->err = "witness completion: the frontier shrank or outgrew its room";
+            return K16_ERR_HIP;
+        }
+        if (f1 == cur.f0) break; // nothing solved: the state the infeasible rows were found in is final
+        bits->n_by_bits += f1 - cur.f0;
+        bits->rounds.push_back(++cur.round);
+        cur.f0 = f1;
+    }
+    *n_rounds = cur.round;
     // the closing pass: the check's own kernels on the completed assignment, then the open constraints' verdicts taken out
     if ((rc = k16_r1cs_launch(r, st, r->d_wtns))) return rc;
     if (M) {
@@ -1051,6 +1431,7 @@ static int r1cs_solve_run(k16_ctx* ctx, k16_r1cs* r, void* h_wtns, uint32_t* n_r
     K16_HIP(ctx, hipGetLastError());
     K16_HIP(ctx, hipMemcpyAsync(V.d_close + 2 * cw + 1, r->d_mask + cw, 8, hipMemcpyDeviceToDevice, st));
     K16_HIP(ctx, hipMemcpyAsync(V.h_close, V.d_close, (2 * cw + 2) * 8, hipMemcpyDeviceToHost, st));
+    if (bits && cw) K16_HIP(ctx, hipMemcpyAsync(r->scans->bits->h_infeasible, r->scans->bits->d_infeasible, cw * 8, hipMemcpyDeviceToHost, st));
     if ((rc = r1cs_det_download(ctx, r, h_round, h_by))) return rc;
     K16_HIP(ctx, hipStreamSynchronize(st));
     if (V.h_close[2 * cw + 1]) { // every value on the device is canonical by now and wire 0 was found to be 1
@@ -1062,17 +1443,31 @@ static int r1cs_solve_run(k16_ctx* ctx, k16_r1cs* r, void* h_wtns, uint32_t* n_r
     return K16_OK;
 }
 
-extern "C" int k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns, const uint32_t* h_given, uint32_t n_given, uint64_t* n_solved,
-                                         uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint64_t* n_failed, uint32_t* h_failed,
-                                         uint32_t cap_failed, uint64_t* n_open_constraints, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
-                                         uint32_t* h_round, uint32_t* h_by)
+// what k16_r1cs_complete_witness_ex returns beyond k16_r1cs_complete_witness
+struct BitsOut {
+    uint64_t *n_by_bits, *n_infeasible;
+    uint32_t* h_infeasible;
+    uint32_t  cap_infeasible;
+    uint8_t*  h_rule;
+};
+
+// both entry points; ex: null for k16_r1cs_complete_witness
+static int r1cs_complete(k16_r1cs* r, void* h_wtns, const uint32_t* h_given, uint32_t n_given, uint32_t rules, uint64_t* n_solved,
+                         uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint64_t* n_failed, uint32_t* h_failed, uint32_t cap_failed,
+                         uint64_t* n_open_constraints, uint32_t* h_wires, uint32_t cap, uint8_t* h_status, uint32_t* h_round, uint32_t* h_by,
+                         const BitsOut* ex)
 {
-    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
     if (!r || !h_wtns || !n_solved || !n_absent || !n_open || !n_rounds || !n_failed || !n_open_constraints || (!h_given && n_given))
         return K16_ERR_ARG;
+    if (ex && (!ex->n_by_bits || !ex->n_infeasible)) return K16_ERR_ARG;
     *n_solved = *n_absent = *n_open = *n_failed = *n_open_constraints = 0;
     *n_rounds                                                        = 0;
-    k16_ctx* ctx                                                     = r->ctx;
+    if (ex) *ex->n_by_bits = *ex->n_infeasible = 0;
+    k16_ctx* ctx = r->ctx;
+    if (rules != K16_SOLVE_RULE_LINEAR && rules != (K16_SOLVE_RULE_LINEAR | K16_SOLVE_RULE_BITS)) {
+        ctx->err = "witness completion: rules is neither K16_SOLVE_RULE_LINEAR nor K16_SOLVE_RULE_LINEAR | K16_SOLVE_RULE_BITS";
+        return K16_ERR_ARG;
+    }
     if (r->forked_on) {
         ctx->err = "witness completion: a prove call is running on the object";
         return K16_ERR_ARG;
@@ -1089,10 +1484,15 @@ extern "C" int k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns, const uint32
             return K16_ERR_ARG;
         }
     }
-    int rc = r1cs_scan_list(ctx, r);
+    const bool with_bits = (rules & K16_SOLVE_RULE_BITS) != 0;
+    int        rc        = r1cs_scan_list(ctx, r);
     if (rc) return rc;
     if ((rc = r1cs_scan_stage(ctx, r->scans->det, [&](ScanDet& S) { return r1cs_det_alloc(ctx, r, S); }))) return rc;
     if ((rc = r1cs_scan_stage(ctx, r->scans->solve, [&](ScanSolve& S) { return r1cs_solve_alloc(ctx, r, S); }))) return rc;
+    if (with_bits) {
+        if ((rc = r1cs_bool_stage(ctx, r))) return rc;
+        if ((rc = r1cs_scan_stage(ctx, r->scans->bits, [&](ScanBits& S) { return r1cs_bits_alloc(ctx, r, S); }))) return rc;
+    }
     const ScanDet&   S     = *r->scans->det;
     const ScanSolve& V     = *r->scans->solve;
     const size_t     words = r->scans->pairs.present.size(), cw = r->n_words;
@@ -1100,7 +1500,15 @@ extern "C" int k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns, const uint32
         ctx->err = why;
         return K16_ERR_ARG;
     }
-    if ((rc = r1cs_scan_drained(ctx, r1cs_solve_run(ctx, r, h_wtns, n_rounds, h_round, h_by)))) {
+    // the rule of a wire is its round's: the rounds are needed for h_rule whether the caller asked for them or not
+    BitsRun               run;
+    std::vector<uint32_t> own_round;
+    uint32_t*             rounds = h_round;
+    if (ex && ex->h_rule && !h_round && with_bits) {
+        own_round.resize(r->n_wires);
+        rounds = own_round.data();
+    }
+    if ((rc = r1cs_scan_drained(ctx, r1cs_solve_run(ctx, r, h_wtns, n_rounds, rounds, h_by, with_bits ? &run : nullptr)))) {
         *n_rounds = 0;
         return rc;
     }
@@ -1114,7 +1522,48 @@ extern "C" int k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns, const uint32
             if (h_failed && failed < cap_failed) h_failed[failed] = (uint32_t)(w * 64u) + (uint32_t)__builtin_ctzll(m);
     }
     *n_failed = failed, *n_open_constraints = open;
+    if (!ex) return K16_OK;
+    *ex->n_by_bits = run.n_by_bits;
+    if (with_bits) {
+        const unsigned long long* inf   = r->scans->bits->h_infeasible;
+        uint64_t                  count = 0, listed = 0;
+        for (size_t w = 0; w < cw; w++) {
+            count += (uint64_t)__builtin_popcountll(inf[w]);
+            if (ex->h_infeasible) listed = r1cs_mask_list(w, inf[w], listed, ex->cap_infeasible, ex->h_infeasible);
+        }
+        *ex->n_infeasible = count;
+    }
+    if (ex->h_rule) {
+        const unsigned long long *seed = S.h_masks, *known = S.h_masks + words;
+        for (uint32_t i = 0; i < r->n_wires; i++) {
+            const bool solved = ((known[i >> 6] & ~seed[i >> 6]) >> (i & 63u)) & 1ull;
+            ex->h_rule[i]     = !solved ? 0 : with_bits && std::binary_search(run.rounds.begin(), run.rounds.end(), rounds[i]) ? 2 : 1;
+        }
+    }
     return K16_OK;
+}
+
+extern "C" int k16_r1cs_complete_witness(k16_r1cs* r, void* h_wtns, const uint32_t* h_given, uint32_t n_given, uint64_t* n_solved,
+                                         uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint64_t* n_failed, uint32_t* h_failed,
+                                         uint32_t cap_failed, uint64_t* n_open_constraints, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
+                                         uint32_t* h_round, uint32_t* h_by)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    return r1cs_complete(r, h_wtns, h_given, n_given, K16_SOLVE_RULE_LINEAR, n_solved, n_absent, n_open, n_rounds, n_failed, h_failed, cap_failed,
+                         n_open_constraints, h_wires, cap, h_status, h_round, h_by, nullptr);
+    });
+}
+
+extern "C" int k16_r1cs_complete_witness_ex(k16_r1cs* r, void* h_wtns, const uint32_t* h_given, uint32_t n_given, uint32_t rules,
+                                            uint64_t* n_solved, uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint64_t* n_failed,
+                                            uint32_t* h_failed, uint32_t cap_failed, uint64_t* n_open_constraints, uint32_t* h_wires, uint32_t cap,
+                                            uint8_t* h_status, uint32_t* h_round, uint32_t* h_by, uint64_t* n_by_bits, uint64_t* n_infeasible,
+                                            uint32_t* h_infeasible, uint32_t cap_infeasible, uint8_t* h_rule)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    const BitsOut ex = {n_by_bits, n_infeasible, h_infeasible, cap_infeasible, h_rule};
+    return r1cs_complete(r, h_wtns, h_given, n_given, rules, n_solved, n_absent, n_open, n_rounds, n_failed, h_failed, cap_failed,
+                         n_open_constraints, h_wires, cap, h_status, h_round, h_by, &ex);
     });
 }
 

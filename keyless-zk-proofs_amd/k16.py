@@ -49,7 +49,7 @@ SYMBOLS = [
     "k16_r1cs_create", "k16_r1cs_create_mem", "k16_r1cs_destroy", "k16_r1cs_info", "k16_r1cs_check_mem", "k16_r1cs_check_file",
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
     "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences", "k16_r1cs_second_values",
-    "k16_r1cs_determined_wires", "k16_r1cs_complete_witness",
+    "k16_r1cs_determined_wires", "k16_r1cs_complete_witness", "k16_r1cs_complete_witness_ex", "k16_r1cs_boolean_wires",
     "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
@@ -183,6 +183,10 @@ def load():
                                             vp, vp, vp]
     L.k16_r1cs_complete_witness.argtypes = [vp, vp, vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32),
                                             C.POINTER(u64), vp, u32, C.POINTER(u64), vp, u32, vp, vp, vp]
+    L.k16_r1cs_complete_witness_ex.argtypes = [vp, vp, vp, u32, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32),
+                                               C.POINTER(u64), vp, u32, C.POINTER(u64), vp, u32, vp, vp, vp, C.POINTER(u64),
+                                               C.POINTER(u64), vp, u32, vp]
+    L.k16_r1cs_boolean_wires.argtypes = [vp, C.POINTER(u64), vp]
     L.k16_prover_set_r1cs.argtypes = [vp, vp]
     L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
     L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
@@ -538,6 +542,7 @@ WIRE_BOUND, WIRE_ABSENT, WIRE_UNBOUND, WIRE_TWO_VALUED = 0, 1, 2, 3
 DET_SEED, DET_DERIVED, DET_ABSENT, DET_OPEN = 0, 1, 2, 3
 DET_NONE = 0xFFFFFFFF
 SOLVE_GIVEN, SOLVE_SOLVED, SOLVE_ABSENT, SOLVE_OPEN = 0, 1, 2, 3
+SOLVE_RULE_LINEAR, SOLVE_RULE_BITS = 1, 2
 
 
 def fullprover_set_r1cs(fullprover, r1cs_path):
@@ -802,14 +807,25 @@ class R1cs:
         out = (int(nd.value), int(na.value), int(no.value), int(nr.value), wires[:min(int(no.value), cap)].copy())
         return out + (status, rounds, by) if want_maps else out
 
-    def complete_witness(self, wtns, given=None, cap=None, cap_failed=None, want_maps=False):
+    def boolean_wires(self, mark=False):
+        """k16_r1cs_boolean_wires: the number of wires some constraint of the circuit holds to {0, 1}; mark=True: (n, ndarray of
+        n_wires uint8, 1 for such a wire).  Needs no check."""
+        n = C.c_uint64()
+        full = np.zeros(self.info()["n_wires"], dtype=np.uint8) if mark else None
+        self.ctx._chk(self.ctx.L.k16_r1cs_boolean_wires(self.h, C.byref(n), _p(full) if mark else None))
+        return (int(n.value), full) if mark else int(n.value)
+
+    def complete_witness(self, wtns, given=None, cap=None, cap_failed=None, want_maps=False, rules=None, cap_infeasible=None):
         """k16_r1cs_complete_witness: the values the given wires force.  wtns: n_wires x 32 bytes, standard form; only the given
         positions (and wire 0 = 1) are read.  given: the wires whose values are given (wire 0 is added); None: the inputs the
         .r1cs header names.  Returns a dict: wtns (a new uint8 array: givens kept, solved values filled in, every other wire 0),
         n_solved, n_absent, n_open, n_rounds, n_failed, n_open_constraints, failed (the lowest min(n_failed, cap_failed) broken
         closed constraints, ascending), wires (the lowest min(n_open, cap) SOLVE_OPEN wires, ascending); None for a cap asks for
         all.  want_maps=True adds status (uint8), round and by (uint32, DET_NONE where there is none) of every wire.  The
-        object is left as check(result["wtns"]) would leave it."""
+        object is left as check(result["wtns"]) would leave it.
+        rules: None for k16_r1cs_complete_witness; SOLVE_RULE_LINEAR or SOLVE_RULE_LINEAR | SOLVE_RULE_BITS for
+        k16_r1cs_complete_witness_ex, which adds n_by_bits, n_infeasible, infeasible (the lowest min(n_infeasible, cap_infeasible)
+        infeasible bit rows of the final state, ascending) and, with want_maps, rule (uint8: 0 none or given, 1 linear, 2 bits)."""
         info = self.info()
         n_wires = info["n_wires"]
         cap = n_wires if cap is None else int(cap)
@@ -829,15 +845,30 @@ class R1cs:
         status = np.zeros(n_wires, dtype=np.uint8) if want_maps else None
         rounds, by = (np.zeros(n_wires, dtype=np.uint32) for _ in range(2)) if want_maps else (None, None)
         ns, na, no, nf, noc, nr = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
-        self.ctx._chk(self.ctx.L.k16_r1cs_complete_witness(
-            self.h, _p(out), _p(given) if given is not None else None, 0 if given is None else n_given, C.byref(ns), C.byref(na),
-            C.byref(no), C.byref(nr), C.byref(nf), _p(failed), cap_failed, C.byref(noc), _p(wires), cap,
-            *((_p(status), _p(rounds), _p(by)) if want_maps else (None, None, None))))
+        head = (self.h, _p(out), _p(given) if given is not None else None, 0 if given is None else n_given)
+        common = (C.byref(ns), C.byref(na), C.byref(no), C.byref(nr), C.byref(nf), _p(failed), cap_failed, C.byref(noc), _p(wires), cap,
+                  *((_p(status), _p(rounds), _p(by)) if want_maps else (None, None, None)))
+        if rules is None:
+            self.ctx._chk(self.ctx.L.k16_r1cs_complete_witness(*head, *common))
+        else:
+            cap_infeasible = info["n_constraints"] if cap_infeasible is None else int(cap_infeasible)
+            if cap_infeasible < 0:
+                raise ValueError("a cap must not be negative")
+            infeasible = np.zeros(max(cap_infeasible, 1), dtype=np.uint32)
+            rule = np.zeros(n_wires, dtype=np.uint8) if want_maps else None
+            nb, ni = C.c_uint64(), C.c_uint64()
+            self.ctx._chk(self.ctx.L.k16_r1cs_complete_witness_ex(*head, int(rules), *common, C.byref(nb), C.byref(ni), _p(infeasible),
+                                                                 cap_infeasible, _p(rule) if want_maps else None))
         res = dict(wtns=out, n_solved=int(ns.value), n_absent=int(na.value), n_open=int(no.value), n_rounds=int(nr.value),
                    n_failed=int(nf.value), n_open_constraints=int(noc.value), failed=failed[:min(int(nf.value), cap_failed)].copy(),
                    wires=wires[:min(int(no.value), cap)].copy())
         if want_maps:
             res.update(status=status, round=rounds, by=by)
+        if rules is not None:
+            res.update(n_by_bits=int(nb.value), n_infeasible=int(ni.value),
+                       infeasible=infeasible[:min(int(ni.value), cap_infeasible)].copy())
+            if want_maps:
+                res.update(rule=rule)
         return res
 
     def wire_constraints(self, wire, cap=None):
