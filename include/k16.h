@@ -770,6 +770,51 @@ int  k16_r1cs_complete_witness_ex(k16_r1cs* r, void* h_wtns, const uint32_t* h_g
                                   uint8_t* h_status, uint32_t* h_round, uint32_t* h_by, uint64_t* n_by_bits, uint64_t* n_infeasible,
                                   uint32_t* h_infeasible, uint32_t cap_infeasible, uint8_t* h_rule /* n_wires bytes, may be NULL */);
 
+/* ---- determinism closure, second rule: the bit decompositions the held booleans force ----
+ * k16_r1cs_determined_wires stops at every constraint with two outside wires, Num2Bits among them, so it calls OPEN what the
+ * completion above proves unique.  k16_r1cs_determined_wires_ex adds the bit rule to the closure.  The closure reads the sums and
+ * the verdicts of the last completed check, never the witness; that a wire holds 0 or 1 in this witness comes from there too:
+ * HELD: a wire x >= 1 is HELD under the last completed check when some constraint that marks x BOOLEAN (above) was not found
+ * broken by it.  Such a row's residual is quad x (x - 1) = 0 with quad != 0: x is 0 or 1 in this witness.  HELD is a subset of
+ * BOOLEAN, and all of it on a satisfying witness.
+ *   k16_r1cs_held_wires   *n_held = how many wires are HELD; h_mark (may be NULL): n_wires bytes, 1 for a HELD wire.  Needs a
+ *                         completed check, like the scans (K16_ERR_ARG without one); its buffers are made by its first call or
+ *                         by the first k16_r1cs_determined_wires_ex call that asks for the bit rule.
+ * THE BIT RULE OF THE CLOSURE, with respect to K: constraint c was not found broken by the last check and has k outside wires
+ * x_1 .. x_k (merged coefficient non-zero, outside K), 2 <= k <= 253.  It applies when
+ *   (a) every x_j is HELD;
+ *   (b) every outside incidence has no A^, or every outside incidence has no B^ (one wire on both sides counts as both): the sum
+ *       of the check that multiplies an unknown is then a sum over K, and lin_j = A^_j b0 + B^_j a0 - C^_j depends on K alone;
+ *   (c) as (c) of the completion's bit rule: lambda is the lin of the LOWEST outside wire, then of the HIGHEST; a lin of 0 is no
+ *       lambda; every lin_j / lambda is 2^(e_j) as a canonical integer, the e_j pairwise distinct and <= 252.  Where neither end
+ *       serves, c gives nothing: part of the definition.
+ * Then every x_j joins K.  There is no feasibility test and no INFEASIBLE class: c is unbroken and the x_j are 0 / 1 in this
+ * witness, so the witness is the expansion.
+ * SOUND: let w' satisfy the circuit and agree with this witness w on K.  w'_j is 0 or 1 by the static marks, w_j by HELD.  Both
+ * residuals of c are 0 and the lin_j depend on K alone, so sum 2^(e_j) (w_j - w'_j) = 0 modulo r; every difference is -1, 0 or
+ * 1 and the sum is below 2^253 < r in absolute value, so it is 0 as an integer, and two 0/1 vectors with the same sum over
+ * distinct powers of two are equal.  Three things the argument needs, none an inefficiency: a BROKEN c derives nothing; a
+ * BOOLEAN wire whose marking rows are all broken is not HELD; a FREE outside incidence (lin_j = 0) fails (c) and keeps the row out.
+ * LEVELS: the PIN rule runs to its fixed point as in k16_r1cs_determined_wires; then ONE bit level examines every constraint with
+ * respect to that K.  The wires it derives get the next round number and by[x] = the LOWEST qualifying c; the PIN rule resumes.
+ * The call ends when a bit level derives nothing.
+ *   rules          K16_DET_RULE_PIN, or K16_DET_RULE_PIN | K16_DET_RULE_BITS; anything else is K16_ERR_ARG before anything is
+ *                  launched (the object keeps the check it had)
+ *   *n_by_bits     required: the wires the bit rule derived
+ *   h_rule (may be NULL)   n_wires bytes: 0 for a seed or underived wire, 1 for the PIN rule, 2 for the bit rule
+ * Every other argument, preconditions, errors, THREADING and state are k16_r1cs_determined_wires's.  With rules =
+ * K16_DET_RULE_PIN the call runs that call's code, allocates nothing beyond it, every output byte is that call's and
+ * *n_by_bits = 0.  One host synchronise per bit level on top of the PIN rounds, at most n_wires - 1 levels.  The constraint-side
+ * index (shared with the completion's bit rule, made by whichever comes first), the marking rows, the HELD mask, the bit
+ * candidates and the rule bytes are made by the first call that asks for the bit rule; the row view of the completion is not
+ * built (csrc/r1cs_scan.hip, csrc/r1cs_bools.h). */
+enum { K16_DET_RULE_PIN = 1, K16_DET_RULE_BITS = 2 };
+int  k16_r1cs_determined_wires_ex(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_seed, uint32_t rules, uint64_t* n_derived,
+                                  uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap,
+                                  uint8_t* h_status, uint32_t* h_round, uint32_t* h_by, uint64_t* n_by_bits,
+                                  uint8_t* h_rule /* n_wires bytes, may be NULL */);
+int  k16_r1cs_held_wires(k16_r1cs* r, uint64_t* n_held, uint8_t* h_mark /* n_wires bytes, may be NULL */);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

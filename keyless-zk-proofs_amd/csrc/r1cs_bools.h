@@ -9,6 +9,8 @@
 //         quad = a1 b1 != 0,   k = a0 b0 - c0 = 0,   lin + quad = 0   (lin = a1 b0 + a0 b1 - c1):
 //     quad x (x - 1), whose roots are exactly 0 and 1 (r is prime).
 // b (b - 1) = 0, b (1 - b) = 0, b b = b and every scaled form of them qualify.  The marks are a function of the circuit alone.
+// Such a constraint is a MARKING ROW of x.  The rows and their wires are handed out too, ascending by constraint: the determinism
+// closure's bit rule (k16_r1cs_held_wires) asks which of them a witness leaves unbroken.
 // Products are Montgomery products (x y / 2^256): every term of a comparison carries the same factor, the C terms through a
 // product with 1, and every operand and result is canonical, so equality of words is equality modulo r.
 #pragma once
@@ -20,6 +22,8 @@ namespace k16 {
 struct R1csBools {
     std::vector<uint64_t> mark; // [ceil(n_wires / 64)] bit i = wire i is BOOLEAN
     uint64_t              n = 0;
+    std::vector<uint32_t> row;      // the marking rows, ascending
+    std::vector<uint32_t> row_wire; // [row.size()] the wire each of them marks
 };
 
 inline void r1cs_bools_build(const R1csFile& f, R1csBools* out)
@@ -33,6 +37,8 @@ inline void r1cs_bools_build(const R1csFile& f, R1csBools* out)
     const R1csFr      zero = {{0, 0, 0, 0}}, one = {{1, 0, 0, 0}};
     out->mark.assign(((size_t)f.n_wires + 63) / 64, 0);
     out->n = 0;
+    out->row.clear();
+    out->row_wire.clear();
     for (uint64_t c = 0; c < M; c++) {
         terms.clear();
         for (uint32_t m = 0; m < 3; m++)
@@ -60,6 +66,8 @@ inline void r1cs_bools_build(const R1csFile& f, R1csBools* out)
         uint64_t& word = out->mark[x >> 6];
         out->n += !((word >> (x & 63)) & 1);
         word |= 1ull << (x & 63);
+        out->row.push_back((uint32_t)c);
+        out->row_wire.push_back(x);
     }
 }
 

@@ -7,6 +7,8 @@
 //   k16_r1cs_complete_witness  which VALUES do the given wires force?  the closure's frontier + k_r1cs_solve_mask, _derive, _commit, _close (10e)
 //   k16_r1cs_complete_witness_ex  ... and which bit decompositions?  k_r1cs_bits_filter, k_r1cs_solve_bits, k_r1cs_bits_commit over the
 //                              boolean marks of k16_r1cs_boolean_wires (r1cs_bools.h) (10f)
+//   k16_r1cs_determined_wires_ex  ... and which wires do the bit decompositions force?  k_r1cs_held, k_r1cs_bits_filter,
+//                              k_r1cs_det_bits over the marking rows the check left unbroken (k16_r1cs_held_wires) (10g)
 // Each kernel is described where it stands.  The list and every buffer here are made by the first call that needs them: create
 // and check calls allocate and launch nothing of this file.  From masks to counts, lists and status bytes: r1cs_masks.h.
 #include <string.h>
@@ -586,6 +588,7 @@ __global__ void __launch_bounds__(256) k_r1cs_solve_close(const unsigned long lo
 // Every operand is < 2r (sums by fradd9 / frsub9, products by frmul9), as in the kernels above.
 constexpr uint32_t BITS_MIN = 2, BITS_MAX = 253; // unknowns of a bit row: exponents 0 .. 252
 constexpr uint32_t BITS_PER_LANE = 4;            // 4 x 64 lanes >= BITS_MAX
+constexpr uint32_t BITS_GRID = 2048;           // workgroups (of one wave) of k_r1cs_solve_bits / k_r1cs_det_bits
 
 // cnt: the outside counts at the fixed point.  total: cleared before the launch.  Launched with whole waves, any grid.
 __global__ void __launch_bounds__(256) k_r1cs_bits_filter(const uint32_t* __restrict__ cnt, uint32_t M, uint32_t* __restrict__ bcand, uint32_t* total)
@@ -804,7 +807,170 @@ __global__ void __launch_bounds__(256) k_r1cs_bits_commit(const uint32_t* __rest
     }
 }
 
-// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Six stages, each made whole by the first call
+// The bit rule of the determinism closure (k16_r1cs_determined_wires_ex with K16_DET_RULE_BITS).  The
+// closure reads the sums and the verdicts of the last completed check, never the witness, so "x is 0 or 1 in this witness" has to
+// come from there as well: a wire x >= 1 is HELD when some marking row of x (r1cs_bools.h) is not broken -- its residual
+// quad x (x - 1) is 0 with quad != 0.  HELD is a subset of BOOLEAN and all of it on a satisfying witness.
+// At the PIN rule's fixed point an unbroken constraint c with k = 2 .. 253 wires x_1 .. x_k outside K gives all of them when
+//   (a) every x_j is HELD,
+//   (b) no outside incidence names A^ or none names B^ (one wire on both sides counts as both): the sum of d_rows that
+//       multiplies an unknown is then a sum over K, and inc_terms' lin_j = A^_j b0 + B^_j a0 - C^_j depends on K alone,
+//   (c) as the completion's (c): lambda = the lin of the LOWEST outside wire, else of the HIGHEST, 0 is no lambda; every
+//       lin_j / lambda is 2^(e_j) as a canonical integer, the e_j distinct and at most 252.
+// SOUND: let w' satisfy the circuit and agree with this witness w on K.  w'_j is 0 or 1 by the static marks, w_j by HELD; both
+// residuals of c are 0 and differ by lambda sum 2^(e_j) (w_j - w'_j): that sum is 0 modulo r, below 2^253 < r in absolute value,
+// so 0 as an integer, and two 0/1 vectors with the same sum over distinct powers of two are equal.  There is no feasibility test:
+// c is unbroken and the x_j are 0/1, so the witness IS the expansion.  Three things that are no inefficiency:
+//   a BROKEN c derives nothing                        its residual is not 0: the difference of the residuals says nothing
+//   a BOOLEAN wire whose marking rows are all broken  is not HELD: its value here need not be 0 or 1
+//   a FREE outside incidence (lin_j = 0)              fails (c), whichever end lambda comes from, and keeps the row out
+//   k_r1cs_held         a lane per marking row: not broken -> its wire's bit in `held` (cleared before the launch; an OR)
+//   k_r1cs_bits_filter  the completion's, unchanged
+//   k_r1cs_det_bits     a wave per candidate, the shape of k_r1cs_solve_bits without the row sums, v, the claims and the commit
+//   k_r1cs_det_expand   the closure's, on the frontier the level appended
+// by[x] is a minimum over the rows that qualify with respect to the level before (`known` and cnt are only read here), the rule
+// byte is written by the one lane that found by[x] empty, and no two levels write one wire: nothing depends on the launch order.
+__global__ void __launch_bounds__(256) k_r1cs_held(const uint32_t* __restrict__ row, const uint32_t* __restrict__ row_wire, uint32_t n,
+                                                   const unsigned long long* __restrict__ verdict, uint32_t M, uint32_t n_wires,
+                                                   unsigned long long* held)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t c = row[i], x = row_wire[i];
+    if (c >= M || x >= n_wires || det_bit(verdict, c)) return;
+    const unsigned long long bit = 1ull << (x & 63u);
+    if (!(__atomic_load_n(&held[x >> 6], __ATOMIC_RELAXED) & bit)) atomicOr(&held[x >> 6], bit); // (bits are only ever set)
+}
+
+// bcand[0 .. *n_bcand): the bit candidates of this level; ONE WAVE per workgroup, a workgroup strides the candidates, every
+// branch is taken by the whole wave, as in k_r1cs_solve_bits.  rule: n_wires bytes, cleared before the first level.
+//   1  the verdict of c, then the gather of the unknown incidences through LDS: slot p in lane p % 64, register p / 64
+//   2  tests (a) and (b): no arithmetic so far
+//   3  lin_j 2^522 from inc_terms: the check's sums, no row is walked
+//   4  lambda's lane runs frinv9, the inverse is broadcast; ratio_j to canonical standard form, the single-bit test
+//   5  the exponents ORed over the wave into a 256-bit mask: its popcount is k exactly when they are distinct
+//   6  atomicMin(by[x], c); the lane that found it empty appends x to the frontier and writes the rule byte
+__global__ void __launch_bounds__(64) k_r1cs_det_bits(const uint32_t* __restrict__ bcand, const uint32_t* __restrict__ n_bcand, const IncList L,
+                                                      const RowIndex X, const unsigned long long* __restrict__ verdict,
+                                                      const unsigned long long* __restrict__ known, const unsigned long long* __restrict__ held,
+                                                      const uint32_t* __restrict__ cnt, uint32_t n_wires, uint32_t* by, uint8_t* __restrict__ rule,
+                                                      uint32_t* __restrict__ front, DetState* st)
+{
+    __shared__ uint32_t slot[BITS_PER_LANE * 64];
+    const uint32_t      lane = threadIdx.x & 63u;
+    const uint32_t      n    = min(*n_bcand, L.M);
+    for (uint32_t w = blockIdx.x; w < n; w += gridDim.x) {
+        const uint32_t c = bcand[w];
+        if (c >= L.M || det_bit(verdict, c)) continue; // a broken row derives nothing
+        const uint32_t k = cnt[c];
+        if (k < BITS_MIN || k > BITS_MAX) continue;
+        // 1: the unknown incidences, in the order of the index
+        const uint32_t cs = X.cstart[c], ce = min(X.cstart[c + 1], L.n_pairs);
+        uint32_t       found = 0;
+        __syncthreads(); // (the slots of the candidate before are read by now)
+        for (uint32_t at = cs; at < ce; at += 64u) {
+            uint32_t idx = DET_NONE;
+            bool     out = false;
+            if (at + lane < ce) {
+                idx = X.cinc[at + lane];
+                if (idx < L.n_pairs) {
+                    const uint32_t x = L.wire[idx];
+                    out              = x < n_wires && L.inc[idx].x == c && !det_bit(known, x);
+                }
+            }
+            const unsigned long long votes = __ballot(out);
+            const uint32_t           pos   = found + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
+            if (out && pos < BITS_PER_LANE * 64u) slot[pos] = idx;
+            found += (uint32_t)__popcll(votes);
+        }
+        __syncthreads();
+        if (found != k) continue; // (cnt counts exactly the incidences outside K)
+        uint32_t x[BITS_PER_LANE];
+        uint4    e[BITS_PER_LANE];
+        bool     ok = true, onA = false, onB = false;
+#pragma unroll
+        for (uint32_t j = 0; j < BITS_PER_LANE; j++) {
+            const uint32_t p = lane + 64u * j;
+            x[j]             = 0;
+            e[j]             = make_uint4(0, R1CS_PAIR_NONE, R1CS_PAIR_NONE, R1CS_PAIR_NONE);
+            if (p < k) {
+                const uint32_t idx = slot[p];
+                x[j]               = L.wire[idx];
+                e[j]               = L.inc[idx];
+                ok                 = ok && det_bit(held, x[j]);   // (a)
+                onA                = onA || e[j].y != R1CS_PAIR_NONE;
+                onB                = onB || e[j].z != R1CS_PAIR_NONE;
+            }
+        }
+        // 2: (a), and (b): with unknowns on A and unknowns on B (one wire on both included) the sums are not sums over K
+        if (__ballot(!ok) || (__ballot(onA) && __ballot(onB))) continue;
+        // 3: lin_j 2^522; by (b) no incidence here names both sides
+        Fr9 one  = fq9_zero();
+        one.l[0] = 1;
+        Fr9 lin[BITS_PER_LANE];
+#pragma unroll
+        for (uint32_t j = 0; j < BITS_PER_LANE; j++) lin[j] = lane + 64u * j < k ? inc_terms(e[j], L).lin : fq9_zero();
+        // 4: lambda: the lin of slot 0 (the lowest unknown wire), then of slot k - 1 (the highest)
+        bool solved = false;
+        for (uint32_t attempt = 0; attempt < 2 && !solved; attempt++) {
+            const uint32_t p = attempt == 0 ? 0u : k - 1u, src = p & 63u, reg = p >> 6;
+            Fr9            lam = lin[0];
+#pragma unroll
+            for (uint32_t j = 1; j < BITS_PER_LANE; j++)
+                if (reg == j) lam = lin[j];
+            lam = wave_bcast9(lam, (int)src);
+            if (!fr9_nonzero(lam)) continue; // (the same value in every lane)
+            Fr9 inv = fq9_zero();
+            if (lane == src) inv = frinv9(frmul9(lam, one));
+            inv = wave_bcast9(inv, (int)src);
+            bool     fits = true;
+            uint32_t mask[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) mask[i] = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < BITS_PER_LANE; j++) {
+                if (lane + 64u * j >= k) continue;
+                const Fr ratio = fr9_to_standard(frmul9(frmul9(lin[j], inv), one));
+                uint32_t pop = 0, at = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    pop += (uint32_t)__popc(ratio.v[i]);
+                    if (ratio.v[i]) at = 32u * i + (uint32_t)__ffs((int)ratio.v[i]) - 1u;
+                }
+                if (pop != 1u || at >= BITS_MAX) {
+                    fits = false;
+                    continue;
+                }
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    if ((at >> 5) == (uint32_t)i) mask[i] |= 1u << (at & 31u);
+            }
+            if (__ballot(!fits)) continue;
+            // 5: distinct exponents
+            uint32_t pop = 0;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) mask[i] |= (uint32_t)__shfl_xor((int)mask[i], d, 64);
+                pop += (uint32_t)__popc(mask[i]);
+            }
+            solved = pop == k;
+        }
+        if (!solved) continue;
+        // 6: every x_j joins K
+#pragma unroll
+        for (uint32_t j = 0; j < BITS_PER_LANE; j++) {
+            bool add = false;
+            if (lane + 64u * j < k) {
+                add = atomicMin(&by[x[j]], c) == DET_NONE;
+                if (add) rule[x[j]] = (uint8_t)K16_DET_RULE_BITS;
+            }
+            wave_append(front, &st->n_front, n_wires, add, x[j]);
+        }
+    }
+}
+
+// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Eight stages, each made whole by the first call
 // that needs it and kept until the object goes; a stage is ready when its pointer is set.
 struct ScanList { // the list on the device, and the unbound-wire scan's mask
     DevBuf<uint4>                 inc;     // R1csPair of every incidence of the wires 1 .. n_wires - 1
@@ -835,9 +1001,18 @@ struct ScanBool { // the boolean marks: a function of the circuit alone
     R1csBools                  host;
     DevBuf<unsigned long long> d_mark; // [ceil(n_wires / 64)]
 };
-struct ScanBits { // the bit rule of the witness completion: on top of the completion's stage
-    DevBuf<uint32_t>              d_cstart;     // [M + 1] the constraint-side index over the device list
-    DevBuf<uint32_t>              d_cinc;       // [n_pairs]
+struct ScanIndex { // the constraint-side index over the device list: by whichever bit rule comes first
+    DevBuf<uint32_t> d_cstart; // [M + 1]
+    DevBuf<uint32_t> d_cinc;   // [n_pairs]
+};
+struct ScanHeld { // HELD and the bit rule of the determinism closure
+    DevBuf<uint32_t>              d_row;   // the marking rows | the wires they mark, [host.row.size()] each
+    DevBuf<unsigned long long>    d_held;  // [ceil(n_wires / 64)]
+    PinnedBuf<unsigned long long> h_held;
+    DevBuf<uint32_t>              d_bcand; // [M] the bit candidates of a level | [1] their number
+    DevBuf<uint8_t>               d_rule;  // [n_wires] K16_DET_RULE_BITS where a bit level derived the wire
+};
+struct ScanBits { // the bit rule of the witness completion: on top of the completion's stage and the index
     DevBuf<uint8_t>               d_claim;      // [n_pairs] the bit a row claimed for the wire of its incidence
     DevBuf<uint32_t>              d_bcand;      // [M] the bit candidates of a level | [1] their number
     DevBuf<unsigned long long>    d_infeasible; // [n_words] the infeasible rows of the last level
@@ -860,7 +1035,9 @@ struct k16::R1csScans {
     std::unique_ptr<ScanDet>    det;
     std::unique_ptr<ScanSolve>  solve;
     std::unique_ptr<ScanBool>   boolean;
+    std::unique_ptr<ScanIndex>  index;
     std::unique_ptr<ScanBits>   bits;
+    std::unique_ptr<ScanHeld>   held;
 };
 void k16::r1cs_scans_delete(R1csScans* s) { delete s; }
 
@@ -952,13 +1129,18 @@ static int r1cs_scan_list(k16_ctx* ctx, k16_r1cs* r)
     return r1cs_scan_stage(ctx, r->scans->list, [&](ScanList& S) { return r1cs_scan_upload(ctx, r, S); });
 }
 // What every diagnostic starts with: a completed check to read, and the list.
-static int r1cs_scan_begin(k16_ctx* ctx, k16_r1cs* r)
+static int r1cs_scan_checked(k16_ctx* ctx, k16_r1cs* r)
 {
     if (!r->have_values || r->forked_on) {
         ctx->err = "no completed check to scan";
         return K16_ERR_ARG;
     }
-    return r1cs_scan_list(ctx, r);
+    return K16_OK;
+}
+static int r1cs_scan_begin(k16_ctx* ctx, k16_r1cs* r)
+{
+    const int rc = r1cs_scan_checked(ctx, r);
+    return rc ? rc : r1cs_scan_list(ctx, r);
 }
 
 // the kernels' view of the device list and of the sums of the last completed check
@@ -1192,56 +1374,89 @@ static int r1cs_det_download(k16_ctx* ctx, k16_r1cs* r, uint32_t* h_round, uint3
     return K16_OK;
 }
 
-// h_masks[0 .. words) holds the seed.  Leaves `known` in h_masks[words ..).
-static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by)
+// The marking rows the last completed check did not find broken, into d_held.  Enqueues only.
+static int r1cs_held_enqueue(k16_ctx* ctx, k16_r1cs* r)
+{
+    const ScanHeld& H     = *r->scans->held;
+    const size_t    words = r->scans->pairs.present.size(), rows = r->scans->boolean->host.row.size();
+    hipStream_t     st    = ctx->stream;
+    K16_HIP(ctx, hipMemsetAsync(H.d_held, 0, std::max<size_t>(words * 8, 8), st));
+    if (rows) {
+        k16_stat_scope sc(ctx, "r1cs_held", st);
+        hipLaunchKernelGGL(k_r1cs_held, r1cs_blocks(rows), dim3(256), 0, st, H.d_row, H.d_row + rows, (uint32_t)rows, r->d_mask, r->M, r->n_wires,
+                           H.d_held);
+    }
+    K16_HIP(ctx, hipGetLastError());
+    return K16_OK;
+}
+
+// h_masks[0 .. words) holds the seed.  Leaves `known` in h_masks[words ..).  n_by_bits: null for the PIN rule alone; else the
+// bit levels are taken (the index, the marks and the held stage are there) and the wires they derived are counted; h_rule then
+// gets the device's rule bytes, K16_DET_RULE_BITS where a bit level derived the wire and 0 elsewhere.
+static int r1cs_det_run(k16_ctx* ctx, k16_r1cs* r, uint32_t* n_rounds, uint32_t* h_round, uint32_t* h_by, uint64_t* n_by_bits, uint8_t* h_rule)
 {
     const ScanDet& S     = *r->scans->det;
     const IncList  L     = r1cs_inc_list(r);
     const size_t   words = r->scans->pairs.present.size();
+    const uint32_t M = r->M, n_wires = r->n_wires;
     hipStream_t    st    = ctx->stream;
     int            rc    = r1cs_det_seed(ctx, r);
     if (rc) return rc;
+    if (n_by_bits) {
+        K16_HIP(ctx, hipMemsetAsync(r->scans->held->d_rule, 0, n_wires, st));
+        if ((rc = r1cs_held_enqueue(ctx, r))) return rc;
+    }
     DetCursor cur;
     *n_rounds = 0;
-    rc        = r1cs_det_rounds(ctx, r, &cur, [&](uint32_t c0, uint32_t c1, uint32_t) {
-        k16_stat_scope sc(ctx, "r1cs_det_derive", st);
-        hipLaunchKernelGGL(k_r1cs_det_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, r->d_mask,
-                           S.d_masks + words, S.d_cnt, S.d_cnt + r->M, r->n_wires, S.d_by, S.d_front, S.d_state);
-        return K16_OK;
-    });
-    if (rc) return rc;
+    // every bit level that goes on adds a wire, and wire 0 is never added: at most n_wires - 1 of them
+    for (uint32_t level = 0;; level++) {
+        // the PIN rule to its fixed point
+        rc = r1cs_det_rounds(ctx, r, &cur, [&](uint32_t c0, uint32_t c1, uint32_t) {
+            k16_stat_scope sc(ctx, "r1cs_det_derive", st);
+            hipLaunchKernelGGL(k_r1cs_det_derive, r1cs_blocks(c1 - c0), dim3(256), 0, st, S.d_cand + c0, c1 - c0, L, r->d_mask,
+                               S.d_masks + words, S.d_cnt, S.d_cnt + M, n_wires, S.d_by, S.d_front, S.d_state);
+            return K16_OK;
+        });
+        if (rc) return rc;
+        // ONE bit level on that state: it is the next round where it derives a wire, and the call's end where it does not
+        if (!n_by_bits || !M || !L.n_pairs || cur.round + 1 >= n_wires) break;
+        if (level + 1 >= n_wires) {
+            ctx->err = "determinism closure: more bit levels than wires";
+            return K16_ERR_HIP;
+        }
+        const ScanHeld&  H       = *r->scans->held;
+        const ScanIndex& X       = *r->scans->index;
+        uint32_t*        d_total = H.d_bcand + M;
+        K16_HIP(ctx, hipMemsetAsync(d_total, 0, 4, st));
+        {
+            k16_stat_scope sc(ctx, "r1cs_det_bits", st);
+            hipLaunchKernelGGL(k_r1cs_bits_filter, r1cs_capped(M), dim3(256), 0, st, S.d_cnt, M, H.d_bcand, d_total);
+            hipLaunchKernelGGL(k_r1cs_det_bits, dim3(std::min(M, BITS_GRID)), dim3(64), 0, st, H.d_bcand, d_total, L,
+                               RowIndex{X.d_cstart, X.d_cinc}, r->d_mask, S.d_masks + words, H.d_held, S.d_cnt, n_wires, S.d_by, H.d_rule,
+                               S.d_front, S.d_state);
+        }
+        {
+            k16_stat_scope sc(ctx, "r1cs_det_expand", st);
+            hipLaunchKernelGGL(k_r1cs_det_expand, r1cs_capped(n_wires), dim3(256), 0, st, S.d_front, cur.f0, cur.round + 1, S.d_start, L, n_wires,
+                               S.d_masks + words, S.d_by + n_wires, S.d_cnt, S.d_cnt + M, S.d_cand, S.d_state, S.rec.dev);
+        }
+        K16_HIP(ctx, hipGetLastError());
+        K16_HIP(ctx, hipStreamSynchronize(st));
+        const uint32_t f1 = S.rec->n_front;
+        if (f1 < cur.f0 || f1 > n_wires) {
+            ctx->err = "determinism closure: the frontier shrank or outgrew its room";
+            return K16_ERR_HIP;
+        }
+        if (f1 == cur.f0) break; // nothing derived: the fixed point of both rules
+        *n_by_bits += f1 - cur.f0;
+        cur.round++;
+        cur.f0 = f1;
+    }
     *n_rounds = cur.round;
     if ((rc = r1cs_det_download(ctx, r, h_round, h_by))) return rc;
+    if (n_by_bits && h_rule) K16_HIP(ctx, hipMemcpyAsync(h_rule, r->scans->held->d_rule, n_wires, hipMemcpyDeviceToHost, st));
     K16_HIP(ctx, hipStreamSynchronize(st));
     return K16_OK;
-}
-
-extern "C" int k16_r1cs_determined_wires(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_seed, uint64_t* n_derived, uint64_t* n_absent,
-                                         uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
-                                         uint32_t* h_round, uint32_t* h_by)
-{
-    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
-    if (!r || !n_derived || !n_absent || !n_open || !n_rounds || (!h_seed && n_seed)) return K16_ERR_ARG;
-    *n_derived = *n_absent = *n_open = 0;
-    *n_rounds                        = 0;
-    k16_ctx* ctx                     = r->ctx;
-    int      rc                      = r1cs_scan_begin(ctx, r);
-    if (rc) return rc;
-    if ((rc = r1cs_scan_stage(ctx, r->scans->det, [&](ScanDet& S) { return r1cs_det_alloc(ctx, r, S); }))) return rc;
-    const ScanDet& S     = *r->scans->det;
-    const size_t   words = r->scans->pairs.present.size();
-    if (const char* why = r1cs_seed_mask(r->n_wires, r->file.n_pub_out, r->file.n_pub_in, r->file.n_prv_in, h_seed, n_seed, S.h_masks)) {
-        ctx->err = why;
-        return K16_ERR_ARG;
-    }
-    if ((rc = r1cs_scan_drained(ctx, r1cs_det_run(ctx, r, n_rounds, h_round, h_by)))) {
-        *n_rounds = 0;
-        return rc;
-    }
-    const uint64_t* present = r->scans->pairs.present.data();
-    r1cs_masks_closure(r->n_wires, present, S.h_masks, S.h_masks + words, n_derived, n_absent, n_open, h_wires, cap, h_status, h_round);
-    return K16_OK;
-    });
 }
 
 // ---- the witness completion
@@ -1302,12 +1517,11 @@ extern "C" int k16_r1cs_boolean_wires(k16_r1cs* r, uint64_t* n_boolean, uint8_t*
     });
 }
 
-// the constraint-side index over the device list (a counting sort keeps the list's order: by wire), the claims, the bit
-// candidates and the infeasible rows
-static int r1cs_bits_alloc(k16_ctx* ctx, k16_r1cs* r, ScanBits& S)
+// the constraint-side index over the device list (a counting sort keeps the list's order: by wire)
+static int r1cs_index_make(k16_ctx* ctx, k16_r1cs* r, ScanIndex& S)
 {
     const R1csPairs&      P    = r->scans->pairs;
-    const size_t          skip = P.start[1], n = r1cs_walked(P), M = r->M, words = r->n_words;
+    const size_t          skip = P.start[1], n = r1cs_walked(P), M = r->M;
     std::vector<uint32_t> cstart(M + 1, 0), cinc(n);
     for (size_t i = 0; i < n; i++)
         if (P.pair[skip + i].constraint < M) cstart[P.pair[skip + i].constraint + 1]++;
@@ -1320,16 +1534,158 @@ static int r1cs_bits_alloc(k16_ctx* ctx, k16_r1cs* r, ScanBits& S)
     int rc;
     if ((rc = r1cs_scan_alloc(ctx, S.d_cstart, (M + 1) * 4))) return rc;
     if ((rc = r1cs_scan_alloc(ctx, S.d_cinc, n * 4))) return rc;
+    hipStream_t st = ctx->stream;
+    K16_HIP(ctx, hipMemcpyAsync(S.d_cstart, cstart.data(), (M + 1) * 4, hipMemcpyHostToDevice, st));
+    if (n) K16_HIP(ctx, hipMemcpyAsync(S.d_cinc, cinc.data(), n * 4, hipMemcpyHostToDevice, st));
+    K16_HIP(ctx, hipStreamSynchronize(st)); // (cstart and cinc are locals)
+    return K16_OK;
+}
+static int r1cs_index_stage(k16_ctx* ctx, k16_r1cs* r)
+{
+    return r1cs_scan_stage(ctx, r->scans->index, [&](ScanIndex& S) { return r1cs_index_make(ctx, r, S); });
+}
+
+// the claims, the bit candidates and the infeasible rows of the completion's bit rule
+static int r1cs_bits_alloc(k16_ctx* ctx, k16_r1cs* r, ScanBits& S)
+{
+    const size_t n = r1cs_walked(r->scans->pairs), M = r->M, words = r->n_words;
+    int          rc;
     if ((rc = r1cs_scan_alloc(ctx, S.d_claim, n))) return rc;
     if ((rc = r1cs_scan_alloc(ctx, S.d_bcand, (M + 1) * 4))) return rc;
     if ((rc = r1cs_scan_alloc(ctx, S.d_infeasible, words * 8))) return rc;
     K16_HIP(ctx, S.h_infeasible.alloc(std::max<size_t>(words * 8, 8)));
-    hipStream_t st = ctx->stream;
-    K16_HIP(ctx, hipMemcpyAsync(S.d_cstart, cstart.data(), (M + 1) * 4, hipMemcpyHostToDevice, st));
-    if (n) K16_HIP(ctx, hipMemcpyAsync(S.d_cinc, cinc.data(), n * 4, hipMemcpyHostToDevice, st));
-    K16_HIP(ctx, hipMemsetAsync(S.d_claim, 0, std::max<size_t>(n, 1), st));
-    K16_HIP(ctx, hipStreamSynchronize(st)); // (cstart and cinc are locals)
+    K16_HIP(ctx, hipMemsetAsync(S.d_claim, 0, std::max<size_t>(n, 1), ctx->stream));
+    K16_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return K16_OK;
+}
+
+// ---- the determinism closure's entry points, HELD
+// the marking rows on the device, the held mask, the closure's bit candidates and rule bytes
+static int r1cs_held_alloc(k16_ctx* ctx, k16_r1cs* r, ScanHeld& S)
+{
+    const R1csBools& B     = r->scans->boolean->host;
+    const size_t     words = r->scans->pairs.present.size(), rows = B.row.size();
+    int              rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_row, 2 * rows * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_held, words * 8))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_bcand, ((size_t)r->M + 1) * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_rule, r->n_wires))) return rc;
+    K16_HIP(ctx, S.h_held.alloc(std::max<size_t>(words * 8, 8)));
+    if (rows) { // (B lives as long as the object: the copies read no local)
+        K16_HIP(ctx, hipMemcpyAsync(S.d_row, B.row.data(), rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        K16_HIP(ctx, hipMemcpyAsync(S.d_row + rows, B.row_wire.data(), rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    K16_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return K16_OK;
+}
+static int r1cs_held_stage(k16_ctx* ctx, k16_r1cs* r)
+{
+    const int rc = r1cs_bool_stage(ctx, r);
+    if (rc) return rc;
+    return r1cs_scan_stage(ctx, r->scans->held, [&](ScanHeld& S) { return r1cs_held_alloc(ctx, r, S); });
+}
+
+extern "C" int k16_r1cs_held_wires(k16_r1cs* r, uint64_t* n_held, uint8_t* h_mark)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_held) return K16_ERR_ARG;
+    *n_held      = 0;
+    k16_ctx* ctx = r->ctx;
+    int      rc  = r1cs_scan_checked(ctx, r);
+    if (rc) return rc;
+    if ((rc = r1cs_held_stage(ctx, r))) return rc;
+    const ScanHeld& H     = *r->scans->held;
+    const size_t    words = r->scans->pairs.present.size();
+    auto            run   = [&]() -> int {
+        const int rc2 = r1cs_held_enqueue(ctx, r);
+        if (rc2) return rc2;
+        if (words) K16_HIP(ctx, hipMemcpyAsync(H.h_held, H.d_held, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        K16_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return K16_OK;
+    };
+    if ((rc = r1cs_scan_drained(ctx, run()))) return rc;
+    uint64_t n = 0;
+    for (size_t w = 0; w < words; w++) n += (uint64_t)__builtin_popcountll(H.h_held[w]);
+    *n_held = n;
+    for (uint32_t i = 0; h_mark && i < r->n_wires; i++) h_mark[i] = (uint8_t)((H.h_held[i >> 6] >> (i & 63u)) & 1u);
+    return K16_OK;
+    });
+}
+
+// The existing entry point keeps a body of its own, the one it had: its host loops over a seed of a million wires and over the
+// masks are a third of a call, and measured 2 to 3 % slower when both entry points shared one function.
+extern "C" int k16_r1cs_determined_wires(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_seed, uint64_t* n_derived, uint64_t* n_absent,
+                                         uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap, uint8_t* h_status,
+                                         uint32_t* h_round, uint32_t* h_by)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_derived || !n_absent || !n_open || !n_rounds || (!h_seed && n_seed)) return K16_ERR_ARG;
+    *n_derived = *n_absent = *n_open = 0;
+    *n_rounds                        = 0;
+    k16_ctx* ctx                     = r->ctx;
+    int      rc                      = r1cs_scan_begin(ctx, r);
+    if (rc) return rc;
+    if ((rc = r1cs_scan_stage(ctx, r->scans->det, [&](ScanDet& S) { return r1cs_det_alloc(ctx, r, S); }))) return rc;
+    const ScanDet& S     = *r->scans->det;
+    const size_t   words = r->scans->pairs.present.size();
+    if (const char* why = r1cs_seed_mask(r->n_wires, r->file.n_pub_out, r->file.n_pub_in, r->file.n_prv_in, h_seed, n_seed, S.h_masks)) {
+        ctx->err = why;
+        return K16_ERR_ARG;
+    }
+    if ((rc = r1cs_scan_drained(ctx, r1cs_det_run(ctx, r, n_rounds, h_round, h_by, nullptr, nullptr)))) {
+        *n_rounds = 0;
+        return rc;
+    }
+    const uint64_t* present = r->scans->pairs.present.data();
+    r1cs_masks_closure(r->n_wires, present, S.h_masks, S.h_masks + words, n_derived, n_absent, n_open, h_wires, cap, h_status, h_round);
+    return K16_OK;
+    });
+}
+
+// The same call with `rules`; K16_DET_RULE_PIN takes the same path through r1cs_det_run.
+extern "C" int k16_r1cs_determined_wires_ex(k16_r1cs* r, const uint32_t* h_seed, uint32_t n_seed, uint32_t rules, uint64_t* n_derived,
+                                            uint64_t* n_absent, uint64_t* n_open, uint32_t* n_rounds, uint32_t* h_wires, uint32_t cap,
+                                            uint8_t* h_status, uint32_t* h_round, uint32_t* h_by, uint64_t* n_by_bits, uint8_t* h_rule)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_derived || !n_absent || !n_open || !n_rounds || !n_by_bits || (!h_seed && n_seed)) return K16_ERR_ARG;
+    *n_derived = *n_absent = *n_open = *n_by_bits = 0;
+    *n_rounds                                    = 0;
+    k16_ctx* ctx                                 = r->ctx;
+    if (rules != K16_DET_RULE_PIN && rules != (K16_DET_RULE_PIN | K16_DET_RULE_BITS)) {
+        ctx->err = "determinism closure: rules is neither K16_DET_RULE_PIN nor K16_DET_RULE_PIN | K16_DET_RULE_BITS";
+        return K16_ERR_ARG;
+    }
+    const bool with_bits = (rules & K16_DET_RULE_BITS) != 0;
+    int        rc        = r1cs_scan_begin(ctx, r);
+    if (rc) return rc;
+    if ((rc = r1cs_scan_stage(ctx, r->scans->det, [&](ScanDet& S) { return r1cs_det_alloc(ctx, r, S); }))) return rc;
+    const ScanDet& S     = *r->scans->det;
+    const size_t   words = r->scans->pairs.present.size();
+    if (const char* why = r1cs_seed_mask(r->n_wires, r->file.n_pub_out, r->file.n_pub_in, r->file.n_prv_in, h_seed, n_seed, S.h_masks)) {
+        ctx->err = why;
+        return K16_ERR_ARG;
+    }
+    if (with_bits) {
+        if ((rc = r1cs_held_stage(ctx, r))) return rc;
+        if ((rc = r1cs_index_stage(ctx, r))) return rc;
+    }
+    if ((rc = r1cs_scan_drained(ctx, r1cs_det_run(ctx, r, n_rounds, h_round, h_by, with_bits ? n_by_bits : nullptr, h_rule)))) {
+        *n_rounds = 0;
+        *n_by_bits = 0;
+        return rc;
+    }
+    const uint64_t* present = r->scans->pairs.present.data();
+    r1cs_masks_closure(r->n_wires, present, S.h_masks, S.h_masks + words, n_derived, n_absent, n_open, h_wires, cap, h_status, h_round);
+    if (h_rule) { // a derived wire that no bit level wrote is the PIN rule's
+        const unsigned long long *seed = S.h_masks, *known = S.h_masks + words;
+        for (uint32_t i = 0; i < r->n_wires; i++) {
+            const bool derived = ((known[i >> 6] & ~seed[i >> 6]) >> (i & 63u)) & 1ull;
+            h_rule[i] = !derived ? 0 : with_bits && h_rule[i] == K16_DET_RULE_BITS ? K16_DET_RULE_BITS : K16_DET_RULE_PIN;
+        }
+    }
+    return K16_OK;
+    });
 }
 
 // what the bit levels of a run did, for the host's maps
@@ -1337,7 +1693,6 @@ struct BitsRun {
     uint64_t              n_by_bits = 0;
     std::vector<uint32_t> rounds; // the rounds that were bit levels, ascending
 };
-constexpr uint32_t BITS_GRID = 2048; // workgroups (of one wave) of k_r1cs_solve_bits
 
 // h_masks[0 .. words) of the closure's stage holds the givens.  K16_ERR_FORMAT before any round when a given value is refused;
 // else leaves the completed assignment in d_wtns and h_wtns, its check in d_rows / d_mask, `known` in h_masks[words ..), and
@@ -1398,7 +1753,7 @@ static int r1cs_solve_run(k16_ctx* ctx, k16_r1cs* r, void* h_wtns, uint32_t* n_r
             k16_stat_scope sc(ctx, "r1cs_solve_bits", st);
             hipLaunchKernelGGL(k_r1cs_bits_filter, r1cs_capped(M), dim3(256), 0, st, S.d_cnt, M, B.d_bcand, d_total);
             hipLaunchKernelGGL(k_r1cs_solve_bits, dim3(std::min(M, BITS_GRID)), dim3(64), 0, st, B.d_bcand, d_total, L, rows,
-                               RowIndex{B.d_cstart, B.d_cinc}, r->d_wtns, S.d_masks + words, r->scans->boolean->d_mark, S.d_cnt, n_wires, S.d_by,
+                               RowIndex{r->scans->index->d_cstart, r->scans->index->d_cinc}, r->d_wtns, S.d_masks + words, r->scans->boolean->d_mark, S.d_cnt, n_wires, S.d_by,
                                B.d_claim, B.d_infeasible, S.d_front, S.d_state);
             hipLaunchKernelGGL(k_r1cs_bits_commit, r1cs_capped(n_wires), dim3(256), 0, st, S.d_front, cur.f0, S.d_state, S.d_by, S.d_start, L,
                                B.d_claim, n_wires, (uint4*)r->d_wtns.p);
@@ -1491,6 +1846,7 @@ static int r1cs_complete(k16_r1cs* r, void* h_wtns, const uint32_t* h_given, uin
     if ((rc = r1cs_scan_stage(ctx, r->scans->solve, [&](ScanSolve& S) { return r1cs_solve_alloc(ctx, r, S); }))) return rc;
     if (with_bits) {
         if ((rc = r1cs_bool_stage(ctx, r))) return rc;
+        if ((rc = r1cs_index_stage(ctx, r))) return rc;
         if ((rc = r1cs_scan_stage(ctx, r->scans->bits, [&](ScanBits& S) { return r1cs_bits_alloc(ctx, r, S); }))) return rc;
     }
     const ScanDet&   S     = *r->scans->det;

@@ -50,6 +50,7 @@ SYMBOLS = [
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
     "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences", "k16_r1cs_second_values",
     "k16_r1cs_determined_wires", "k16_r1cs_complete_witness", "k16_r1cs_complete_witness_ex", "k16_r1cs_boolean_wires",
+    "k16_r1cs_determined_wires_ex", "k16_r1cs_held_wires",
     "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
@@ -187,6 +188,9 @@ def load():
                                                C.POINTER(u64), vp, u32, C.POINTER(u64), vp, u32, vp, vp, vp, C.POINTER(u64),
                                                C.POINTER(u64), vp, u32, vp]
     L.k16_r1cs_boolean_wires.argtypes = [vp, C.POINTER(u64), vp]
+    L.k16_r1cs_determined_wires_ex.argtypes = [vp, vp, u32, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), vp, u32,
+                                               vp, vp, vp, C.POINTER(u64), vp]
+    L.k16_r1cs_held_wires.argtypes = [vp, C.POINTER(u64), vp]
     L.k16_prover_set_r1cs.argtypes = [vp, vp]
     L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
     L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
@@ -543,6 +547,7 @@ DET_SEED, DET_DERIVED, DET_ABSENT, DET_OPEN = 0, 1, 2, 3
 DET_NONE = 0xFFFFFFFF
 SOLVE_GIVEN, SOLVE_SOLVED, SOLVE_ABSENT, SOLVE_OPEN = 0, 1, 2, 3
 SOLVE_RULE_LINEAR, SOLVE_RULE_BITS = 1, 2
+DET_RULE_PIN, DET_RULE_BITS = 1, 2
 
 
 def fullprover_set_r1cs(fullprover, r1cs_path):
@@ -783,11 +788,14 @@ class R1cs:
         out = (int(n.value), wires[:k].copy(), [int.from_bytes(shifts[i].tobytes(), "little") for i in range(k)])
         return out + (full,) if status else out
 
-    def determined_wires(self, seed=None, cap=None, want_maps=False):
+    def determined_wires(self, seed=None, cap=None, want_maps=False, rules=None):
         """k16_r1cs_determined_wires on the sums of the last completed check: (n_derived, n_absent, n_open, n_rounds, wires) with
         the lowest min(n_open, cap) DET_OPEN wires, ascending; cap=None asks for all of them.  seed: the wires whose values are
         given (wire 0 is added); None: the inputs the .r1cs header names.  want_maps=True appends the class of every wire
-        (uint8), its round and its deriving constraint (uint32, DET_NONE where there is none)."""
+        (uint8), its round and its deriving constraint (uint32, DET_NONE where there is none).
+        rules: None for k16_r1cs_determined_wires; DET_RULE_PIN or DET_RULE_PIN | DET_RULE_BITS for
+        k16_r1cs_determined_wires_ex, whose result gains n_by_bits at the end and, with want_maps, rule (uint8: 0 seed or
+        underived, 1 the PIN rule, 2 the bit rule) behind it."""
         n_wires = self.info()["n_wires"]
         cap = n_wires if cap is None else int(cap)
         if cap < 0:
@@ -801,11 +809,29 @@ class R1cs:
         status = np.zeros(n_wires, dtype=np.uint8) if want_maps else None
         rounds, by = (np.zeros(n_wires, dtype=np.uint32) for _ in range(2)) if want_maps else (None, None)
         nd, na, no, nr = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
-        self.ctx._chk(self.ctx.L.k16_r1cs_determined_wires(
-            self.h, _p(seed) if seed is not None else None, 0 if seed is None else n_seed, C.byref(nd), C.byref(na),
-            C.byref(no), C.byref(nr), _p(wires), cap, *((_p(status), _p(rounds), _p(by)) if want_maps else (None, None, None))))
+        head = (self.h, _p(seed) if seed is not None else None, 0 if seed is None else n_seed)
+        common = (C.byref(nd), C.byref(na), C.byref(no), C.byref(nr), _p(wires), cap,
+                  *((_p(status), _p(rounds), _p(by)) if want_maps else (None, None, None)))
+        if rules is None:
+            self.ctx._chk(self.ctx.L.k16_r1cs_determined_wires(*head, *common))
+        else:
+            nb = C.c_uint64()
+            rule = np.zeros(n_wires, dtype=np.uint8) if want_maps else None
+            self.ctx._chk(self.ctx.L.k16_r1cs_determined_wires_ex(*head, int(rules), *common, C.byref(nb), _p(rule) if want_maps else None))
         out = (int(nd.value), int(na.value), int(no.value), int(nr.value), wires[:min(int(no.value), cap)].copy())
-        return out + (status, rounds, by) if want_maps else out
+        if want_maps:
+            out += (status, rounds, by)
+        if rules is not None:
+            out += (int(nb.value),) + ((rule,) if want_maps else ())
+        return out
+
+    def held_wires(self, mark=False):
+        """k16_r1cs_held_wires: the number of wires HELD under the last completed check -- some constraint that marks the wire
+        BOOLEAN was not found broken; mark=True: (n, ndarray of n_wires uint8, 1 for such a wire)."""
+        n = C.c_uint64()
+        full = np.zeros(self.info()["n_wires"], dtype=np.uint8) if mark else None
+        self.ctx._chk(self.ctx.L.k16_r1cs_held_wires(self.h, C.byref(n), _p(full) if mark else None))
+        return (int(n.value), full) if mark else int(n.value)
 
     def boolean_wires(self, mark=False):
         """k16_r1cs_boolean_wires: the number of wires some constraint of the circuit holds to {0, 1}; mark=True: (n, ndarray of
