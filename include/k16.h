@@ -815,6 +815,64 @@ int  k16_r1cs_determined_wires_ex(k16_r1cs* r, const uint32_t* h_seed, uint32_t 
                                   uint8_t* h_rule /* n_wires bytes, may be NULL */);
 int  k16_r1cs_held_wires(k16_r1cs* r, uint64_t* n_held, uint8_t* h_mark /* n_wires bytes, may be NULL */);
 
+/* ---- the open-set solve: rank and null space of what a closure leaves open ----
+ * The closure derives a wire only when ONE constraint pins it.  x + y = s1, x - y = s2 force both wires, yet every constraint
+ * has two outside wires: both stay OPEN.  Wherever the constraints are LINEAR in the open wires the question "forced, or what
+ * is the second witness?" has an exact answer, by linear algebra over Fr on the Jacobian of the residuals at this witness.
+ * Reads the sums and the verdicts of the last completed check, as the scans do.
+ *   h_fixed     n_wires bytes, non-zero = the wire is held FIXED; wire 0 always is.  Typically status != K16_DET_OPEN of a
+ *               closure; any mask is legal.  An OUTSIDE wire is one that is not fixed.
+ *   DROPPED     a constraint the last check found broken gives no equation and no connectivity (the closure's rule)
+ *   LINEAR / CROSS   an unbroken constraint with an outside incidence is LINEAR when its outside wires with A^ != 0 or its outside
+ *               wires with B^ != 0 are none, CROSS otherwise (x * x = y with x outside is CROSS: two-valued, never forced).
+ *               Moving the outside wires by t moves the residual of a LINEAR constraint by exactly sum_x lin(x, c) t_x,
+ *               lin = A^ b_c + B^ a_c - C^ as in the scans.
+ *   COMPONENTS  of the bipartite graph of outside wires and unbroken constraints, LINEAR and CROSS alike; a component's id is its
+ *               lowest wire; EXACT: it has no CROSS constraint.  An outside wire whose incidences all lie in broken constraints
+ *               is a component of one wire and no rows.
+ *   J, R, rank  J: rows = the component's LINEAR constraints, columns = its wires ascending, entries lin mod r.  R: its reduced
+ *               row echelon form for that column order (unique, whatever the row order); rank: its pivots.
+ * One byte per wire:
+ *   K16_OPEN_FIXED      in h_fixed, or wire 0
+ *   K16_OPEN_ABSENT     outside and in no term of any constraint (structural, as K16_WIRE_ABSENT)
+ *   K16_OPEN_FORCED     e_x lies in the row space of J: x is a pivot column whose row of R is zero in every non-pivot column
+ *   K16_OPEN_FREE       not FORCED, component EXACT
+ *   K16_OPEN_UNDECIDED  not FORCED, the component has a CROSS constraint
+ *   K16_OPEN_SKIPPED    the component has more than K16_OPEN_MAX_WIRES wires: not eliminated
+ * SOUND: any witness that satisfies the circuit and agrees with this one on the fixed wires agrees with it on every FORCED wire
+ * (in EXACT components and others alike: only LINEAR rows are used).  EXACT on EXACT components: every FREE wire x has a direction
+ * d with d_x != 0, supported on its component, such that w + d leaves the residual of every unbroken constraint at zero.  The
+ * call judges nothing: a FREE mux input behind a zero selector is legitimate.
+ * The CANONICAL direction of a FREE wire x: F = the non-pivot columns; for f in F, v_f[f] = 1, v_f[f'] = 0 for the other free
+ * columns, v_f[p] = -R[row(p)][f] for pivot columns.  x in F: d = v_x; else f = the lowest free column with R[row(x)][f] != 0 and
+ * d = v_f / v_f[x].  So d_x = 1; the bytes are the same on every run and for every order of the constraints in the file.
+ *   k16_r1cs_open_system     *n_forced .. *n_absent: wires of each class; *n_components: all components, SKIPPED ones included;
+ *                            *n_dims: the sum of (wires - rank) over the EXACT components that were eliminated.  h_wires /
+ *                            h_class (may be NULL): the lowest min(cap, n_forced + n_free + n_undecided + n_skipped) wires that
+ *                            are neither FIXED nor ABSENT, ascending, with their class.  h_status (may be NULL): n_wires
+ *                            bytes, the class of every wire.  h_comp (may be NULL): n_wires words, the lowest wire of the
+ *                            wire's component, 0xffffffff for FIXED / ABSENT.
+ *   k16_r1cs_open_direction  stateless: finds `wire`'s component on the host from h_fixed and eliminates that one component.
+ *                            *cls: the wire's class; *comp_wires / *comp_rows / *comp_cross (may be NULL): the component's wires,
+ *                            LINEAR rows and CROSS constraints (0 for FIXED / ABSENT); *rank (may be NULL; 0 for SKIPPED);
+ *                            *n: the non-zeros of d, 0 unless the wire is FREE; h_wires / h_vals (may be NULL): the lowest
+ *                            min(*n, cap) wires with d != 0, ascending, and their values, 32 bytes each, standard form,
+ *                            little-endian, canonical.  Add d to the witness and k16_r1cs_check_mem finds what it found.
+ * Preconditions, errors and THREADING as k16_r1cs_unbound_wires: K16_ERR_ARG when no check has completed on r, while a prove call
+ * runs on an attached object, for h_fixed == NULL and for wire >= nWires; every error leaves nothing in flight.  The components
+ * are found on the host (one walk over the outside wires' incidences); the elimination is k_r1cs_open_rref, one wave per
+ * component, one launch per size class (<= 16, <= 32, <= 64 wires).  The constraint-side index and every buffer are made by the
+ * first call and stay with the object (csrc/r1cs_open.h, csrc/r1cs_scan.hip). */
+#define K16_OPEN_MAX_WIRES 64
+enum { K16_OPEN_FIXED = 0, K16_OPEN_ABSENT = 1, K16_OPEN_FORCED = 2, K16_OPEN_FREE = 3, K16_OPEN_UNDECIDED = 4, K16_OPEN_SKIPPED = 5 };
+int  k16_r1cs_open_system(k16_r1cs* r, const uint8_t* h_fixed, uint64_t* n_forced, uint64_t* n_free, uint64_t* n_undecided,
+                          uint64_t* n_skipped, uint64_t* n_absent, uint64_t* n_components, uint64_t* n_dims, uint32_t* h_wires,
+                          uint8_t* h_class, uint32_t cap, uint8_t* h_status /* n_wires bytes, may be NULL */,
+                          uint32_t* h_comp /* n_wires words, may be NULL */);
+int  k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint32_t wire, uint8_t* cls, uint32_t* comp_wires,
+                             uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n, uint32_t* h_wires,
+                             uint8_t* h_vals /* 32 B each */, uint32_t cap);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

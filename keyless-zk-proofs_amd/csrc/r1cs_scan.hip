@@ -19,6 +19,7 @@
 #include "frinv_dev.h"
 #include "r1cs_bools.h"
 #include "r1cs_masks.h"
+#include "r1cs_open.h"
 #include "r1cs_pairs.h"
 #include "r1cs_rows.h"
 #include "spmv_dev.h"
@@ -970,7 +971,158 @@ __global__ void __launch_bounds__(64) k_r1cs_det_bits(const uint32_t* __restrict
     }
 }
 
-// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Eight stages, each made whole by the first call
+// The open-set solve (k16_r1cs_open_system, k16_r1cs_open_direction): rank and null space of what a
+// closure leaves open.  The host (r1cs_open.h) cuts the outside wires into components and lists, per component of at most 64
+// wires, its LINEAR rows; the matrix J of a component has those rows, the component's wires (ascending) as columns and the
+// incidences' lin as entries.  k_r1cs_open_rref brings J to its reduced row echelon form R, ONE WAVE per component, lane j
+// owning column j.  A wire x is FORCED when e_x lies in the row space: x is a pivot column and its row of R is zero in every
+// non-pivot column.
+//   the basis      rank rows, kept REDUCED at every step (a 1 in the own pivot column, 0 in every other pivot column), in LDS
+//                  as basis[row][limb][column]: the lanes of a wave read and write neighbouring banks
+//   a row of J     its entries are computed lane-parallel (inc_terms) and scattered into a zeroed row vector in LDS; lane j
+//                  then holds entry j.  Reduced against the basis: the factors are the row's OWN entries in the pivot columns
+//                  (the basis being reduced, no factor depends on another subtraction): rank multiply-subtracts per lane
+//   the remainder  zero mod r in every column (fr9_nonzero: lazy representatives below 2r) -> the row is discarded; else its
+//                  lowest non-zero column p becomes a pivot (ballot, count): lane p runs frinv9, the inverse is broadcast, the
+//                  row is normalised, column p is cleared from every basis row, the row is inserted.  Pivots are leading
+//                  entries: a basis row is zero below its pivot when it enters, and every later row added to it starts at a
+//                  higher column or has factor zero -- so the end state is THE reduced row echelon form, whatever the row order
+// Every loop bound is a count the host wrote (components, rows, entries) or the rank, which grows by one per inserted row and
+// cannot pass the number of columns.  Nothing iterates until nothing changes.
+// Scalings: inc_terms gives lin 2^522 = (lin 2^261) 2^261, the R' value of lin 2^261.  Every row of J carries the same extra
+// factor 2^261, which changes neither row space nor R; the elimination is plain R' arithmetic (frmul9 of two R' values is the
+// R' value of the product, frinv9 of an R' value that of the inverse).  Operands: sums and differences < 2r by fradd9 / frsub9,
+// products < 2r by frmul9.  An entry of R leaves through fr9_to_standard: canonical standard form.
+// With `emit` (one component, k16_r1cs_open_direction) the canonical direction d of column emit_col is written as 64 values:
+//   F the free columns; v_f[f] = 1, v_f[f'] = 0, v_f[p] = -R[row(p)][f];  x free: d = v_x;  x a pivot: f = the lowest free column
+//   with R[row(x)][f] != 0 and d = v_f / v_f[x] (one more inversion, on lane x).  All zero where x is FORCED.
+struct OpenJob {
+    const R1csOpenComp* __restrict__ comp;       // the components of this launch
+    uint32_t n_comp;
+    const uint32_t* __restrict__ row_start;      // [n_rows + 1]
+    const uint2* __restrict__ ent;               // [n_ent] (column, incidence)
+    uint32_t n_rows, n_ent, n_wires;             // the sizes of row_start, ent and cls: nothing is read or written beyond them
+    unsigned long long* __restrict__ out;        // per component of the launch: rank | pivot mask | FORCED mask
+    uint8_t* __restrict__ cls;                   // [n_wires] by position in the work list's wires
+    Fr* __restrict__ emit;                       // null, or 64 values
+    uint32_t emit_col;
+};
+static_assert(sizeof(R1csOpenComp) == 24 && sizeof(R1csOpenEntry) == sizeof(uint2), "the work list is uploaded as it is");
+
+template <uint32_t W>
+__global__ void __launch_bounds__(64) k_r1cs_open_rref(const IncList L, const OpenJob J)
+{
+    __shared__ uint32_t basis[W * 9 * W]; // [(row * 9 + limb) * W + column]
+    __shared__ uint32_t rowv[9 * W];      // [limb * W + column]
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool     mine = lane < W; // (lanes beyond the class's width hold no column)
+    const uint32_t own_col = mine ? lane : 0u; // what such a lane may index the basis with: no load leaves the array, used or not
+    auto load_basis = [&](uint32_t row, uint32_t col) {
+        Fr9 b;
+#pragma unroll
+        for (int i = 0; i < 9; i++) b.l[i] = basis[(row * 9u + i) * W + col];
+        return b;
+    };
+    for (uint32_t k = blockIdx.x; k < J.n_comp; k += gridDim.x) {
+        const R1csOpenComp C  = J.comp[k];
+        const uint32_t     nw = min(C.n_wires, W);
+        const bool         col = lane < nw;
+        uint32_t           rank = 0, my_pivot = 0, my_row = 0; // lane k: the pivot of basis row k; lane j: the row of pivot column j
+        unsigned long long pivots = 0;
+        for (uint32_t r = 0; r < C.n_rows; r++) {
+            if (C.row0 + r >= J.n_rows) break; // (the same in every lane)
+            const uint32_t rs = J.row_start[C.row0 + r], re = min(J.row_start[C.row0 + r + 1], J.n_ent);
+            const uint32_t len = re > rs ? min(re - rs, W) : 0;
+            __syncthreads(); // (the row before is read by now)
+            if (mine) {
+#pragma unroll
+                for (int i = 0; i < 9; i++) rowv[i * W + lane] = 0;
+            }
+            __syncthreads();
+            if (lane < len) {
+                const uint2 e = J.ent[rs + lane];
+                if (e.x < nw && e.y < L.n_pairs) {
+                    const IncTerms t = inc_terms(L.inc[e.y], L);
+#pragma unroll
+                    for (int i = 0; i < 9; i++) rowv[i * W + e.x] = t.lin.l[i];
+                }
+            }
+            __syncthreads();
+            Fr9 v = fq9_zero();
+            if (mine) {
+#pragma unroll
+                for (int i = 0; i < 9; i++) v.l[i] = rowv[i * W + lane];
+            }
+            const Fr9 own = v;
+            for (uint32_t b = 0; b < rank; b++) {
+                const Fr9 f = wave_bcast9(own, (int)__shfl(my_pivot, (int)b, 64));
+                if (mine) v = frsub9(v, frmul9(f, load_basis(b, lane)));
+            }
+            const unsigned long long live = __ballot(col && !((pivots >> lane) & 1ull) && fr9_nonzero(v));
+            if (!live || rank >= W) continue; // in the row space already
+            const uint32_t p = (uint32_t)__ffsll((long long)live) - 1u;
+            Fr9            inv = fq9_zero();
+            if (lane == p) inv = frinv9(v);
+            inv = wave_bcast9(inv, (int)p);
+            v   = frmul9(v, inv);
+            for (uint32_t b = 0; b < rank; b++) {
+                const Fr9 f = load_basis(b, p); // (one address for the wave: a broadcast read)
+                if (mine) {
+                    const Fr9 c = frsub9(load_basis(b, lane), frmul9(f, v));
+#pragma unroll
+                    for (int i = 0; i < 9; i++) basis[(b * 9u + i) * W + lane] = c.l[i];
+                }
+            }
+            if (mine) {
+#pragma unroll
+                for (int i = 0; i < 9; i++) basis[(rank * 9u + i) * W + lane] = v.l[i];
+            }
+            if (lane == rank) my_pivot = p;
+            if (lane == p) my_row = rank;
+            pivots |= 1ull << p;
+            rank++;
+        }
+        __syncthreads();
+        // FORCED: a pivot whose row is zero in every free column
+        unsigned long long forced = 0;
+        for (uint32_t b = 0; b < rank; b++) {
+            const uint32_t p = __shfl(my_pivot, (int)b, 64);
+            if (!__ballot(col && !((pivots >> lane) & 1ull) && fr9_nonzero(load_basis(b, own_col)))) forced |= 1ull << p;
+        }
+        if (lane == 0) {
+            J.out[3 * (size_t)k]     = rank;
+            J.out[3 * (size_t)k + 1] = pivots;
+            J.out[3 * (size_t)k + 2] = forced;
+        }
+        if (col && (uint64_t)C.wire0 + lane < J.n_wires)
+            J.cls[C.wire0 + lane] = (uint8_t)((forced >> lane) & 1ull ? K16_OPEN_FORCED : C.n_cross ? K16_OPEN_UNDECIDED : K16_OPEN_FREE);
+        if (J.emit) {
+            const uint32_t x    = min(J.emit_col, 63u);
+            uint32_t       f    = x;
+            bool           have = x < nw && !((forced >> x) & 1ull);
+            const bool     on_pivot = (pivots >> x) & 1ull;
+            if (on_pivot) { // the lowest free column in x's row
+                const uint32_t           row  = __shfl(my_row, (int)x, 64);
+                const unsigned long long free = __ballot(col && !((pivots >> lane) & 1ull) && row < rank && fr9_nonzero(load_basis(row < rank ? row : 0u, own_col)));
+                have = have && free != 0;
+                f    = free ? (uint32_t)__ffsll((long long)free) - 1u : 0u;
+            }
+            Fr9 d = fq9_zero();
+            if (have && col) {
+                if (lane == f) d = fr9_one();
+                else if ((pivots >> lane) & 1ull) d = frsub9(fq9_zero(), load_basis(my_row, f));
+            }
+            if (have && on_pivot) { // (the same branch in every lane)
+                Fr9 inv = fq9_zero();
+                if (lane == x) inv = frinv9(d);
+                d = frmul9(d, wave_bcast9(inv, (int)x));
+            }
+            st_fr(&J.emit[lane], fr9_to_standard(d));
+        }
+    }
+}
+
+// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Nine stages, each made whole by the first call
 // that needs it and kept until the object goes; a stage is ready when its pointer is set.
 struct ScanList { // the list on the device, and the unbound-wire scan's mask
     DevBuf<uint4>                 inc;     // R1csPair of every incidence of the wires 1 .. n_wires - 1
@@ -1025,6 +1177,20 @@ struct ScanSolve { // the witness completion: on top of the closure's stage
     DevBuf<unsigned long long>    d_close;    // judged | open, [n_words] each | [1] the flags of k_r1cs_solve_mask | [1] the check's
     PinnedBuf<unsigned long long> h_close;
 };
+struct ScanOpen { // the open-set solve: every size is bounded by the circuit's, so the buffers are made once
+    R1csOpenIndex                 index;     // the constraint-side index over the host list
+    R1csOpenWork                  work;      // the work list of the last call
+    PinnedBuf<unsigned long long> h_verdict; // [n_words] the check's verdicts
+    DevBuf<R1csOpenComp>          d_comp;    // [n_wires]
+    DevBuf<uint32_t>              d_rowstart; // [M + 1]
+    DevBuf<uint2>                 d_ent;     // [n_pairs]
+    DevBuf<unsigned long long>    d_out;     // [3 n_wires] rank | pivot mask | FORCED mask of every component
+    PinnedBuf<unsigned long long> h_out;
+    DevBuf<uint8_t>               d_cls;     // [n_wires] the classes, by position in the work list's wires
+    PinnedBuf<uint8_t>            h_cls;
+    DevBuf<Fr>                    d_emit;    // [64] a direction
+    PinnedBuf<Fr>                 h_emit;
+};
 
 } // namespace
 
@@ -1038,6 +1204,7 @@ struct k16::R1csScans {
     std::unique_ptr<ScanIndex>  index;
     std::unique_ptr<ScanBits>   bits;
     std::unique_ptr<ScanHeld>   held;
+    std::unique_ptr<ScanOpen>   open;
 };
 void k16::r1cs_scans_delete(R1csScans* s) { delete s; }
 
@@ -1920,6 +2087,189 @@ extern "C" int k16_r1cs_complete_witness_ex(k16_r1cs* r, void* h_wtns, const uin
     const BitsOut ex = {n_by_bits, n_infeasible, h_infeasible, cap_infeasible, h_rule};
     return r1cs_complete(r, h_wtns, h_given, n_given, rules, n_solved, n_absent, n_open, n_rounds, n_failed, h_failed, cap_failed,
                          n_open_constraints, h_wires, cap, h_status, h_round, h_by, &ex);
+    });
+}
+
+// ---- the open-set solve
+constexpr uint32_t OPEN_GRID = 4096; // workgroups (of one wave) of a launch of k_r1cs_open_rref: a workgroup strides the components
+
+// the constraint-side index on the host and every buffer: their sizes are bounded by the circuit's (a component has a wire, a
+// row is a constraint, an entry an incidence), so one allocation serves every mask
+static int r1cs_open_alloc(k16_ctx* ctx, k16_r1cs* r, ScanOpen& S)
+{
+    const R1csPairs& P = r->scans->pairs;
+    const size_t     n = r->n_wires, M = r->M, np = r1cs_walked(P), words = r->n_words;
+    r1cs_open_index(P, r->M, &S.index);
+    int rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_comp, n * sizeof(R1csOpenComp)))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_rowstart, (M + 1) * 4))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_ent, np * sizeof(uint2)))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_out, 3 * n * 8))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_cls, n))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_emit, 64 * sizeof(Fr)))) return rc;
+    K16_HIP(ctx, S.h_verdict.alloc(std::max<size_t>(words * 8, 8)));
+    K16_HIP(ctx, S.h_out.alloc(std::max<size_t>(3 * n * 8, 8)));
+    K16_HIP(ctx, S.h_cls.alloc(std::max<size_t>(n, 8)));
+    K16_HIP(ctx, S.h_emit.alloc(64 * sizeof(Fr)));
+    return K16_OK;
+}
+
+// What both entry points start with: a completed check, the list, the stage, the fixed mask and the check's verdicts on the host.
+static int r1cs_open_begin(k16_ctx* ctx, k16_r1cs* r, const uint8_t* h_fixed)
+{
+    int rc = r1cs_scan_checked(ctx, r);
+    if (rc) return rc;
+    if (!h_fixed) {
+        ctx->err = "open-set solve: no mask of fixed wires";
+        return K16_ERR_ARG;
+    }
+    if ((rc = r1cs_scan_list(ctx, r))) return rc;
+    if ((rc = r1cs_scan_stage(ctx, r->scans->open, [&](ScanOpen& S) { return r1cs_open_alloc(ctx, r, S); }))) return rc;
+    const ScanOpen& S = *r->scans->open;
+    memset(S.h_verdict, 0, std::max<size_t>((size_t)r->n_words * 8, 8));
+    auto get = [&]() -> int {
+        if (r->n_words) K16_HIP(ctx, hipMemcpyAsync(S.h_verdict, r->d_mask, (size_t)r->n_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        K16_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return K16_OK;
+    };
+    return r1cs_scan_drained(ctx, get());
+}
+
+template <uint32_t W>
+static void r1cs_open_launch(k16_ctx* ctx, const char* name, const IncList& L, OpenJob J, uint32_t first, uint32_t n)
+{
+    if (!n) return;
+    J.comp += first;
+    J.out += 3 * (size_t)first;
+    J.n_comp = n;
+    k16_stat_scope sc(ctx, name, ctx->stream);
+    hipLaunchKernelGGL(k_r1cs_open_rref<W>, dim3(std::min(n, OPEN_GRID)), dim3(64), 0, ctx->stream, L, J);
+}
+
+// The work list up, one launch per size class, ranks, masks and classes (and the direction of column emit_col, where asked) down.
+static int r1cs_open_run(k16_ctx* ctx, k16_r1cs* r, bool emit, uint32_t emit_col)
+{
+    const ScanOpen&     S  = *r->scans->open;
+    const R1csOpenWork& Wk = S.work;
+    const size_t        nc = Wk.comps.size(), nw = Wk.wires.size(), nr = Wk.row.size(), ne = Wk.ent.size();
+    if (!nc) return K16_OK;
+    if (nc > r->n_wires || nw > r->n_wires || nr > r->M || ne > r1cs_walked(r->scans->pairs)) {
+        ctx->err = "open-set solve: the work list outgrew the circuit";
+        return K16_ERR_HIP;
+    }
+    hipStream_t st = ctx->stream;
+    {
+        k16_stat_scope sc(ctx, "r1cs_open_upload", st);
+        K16_HIP(ctx, hipMemcpyAsync(S.d_comp, Wk.comps.data(), nc * sizeof(R1csOpenComp), hipMemcpyHostToDevice, st));
+        K16_HIP(ctx, hipMemcpyAsync(S.d_rowstart, Wk.row_start.data(), (nr + 1) * 4, hipMemcpyHostToDevice, st));
+        if (ne) K16_HIP(ctx, hipMemcpyAsync(S.d_ent, Wk.ent.data(), ne * sizeof(R1csOpenEntry), hipMemcpyHostToDevice, st));
+        K16_HIP(ctx, hipMemsetAsync(S.d_cls, 0xff, nw, st));
+    }
+    const IncList L = r1cs_inc_list(r);
+    const OpenJob J{S.d_comp, 0, S.d_rowstart, S.d_ent, (uint32_t)nr, (uint32_t)ne, (uint32_t)nw, S.d_out, S.d_cls, emit ? S.d_emit.p : nullptr, emit_col};
+    r1cs_open_launch<16>(ctx, "r1cs_open_rref16", L, J, 0, Wk.n_class[0]);
+    r1cs_open_launch<32>(ctx, "r1cs_open_rref32", L, J, Wk.n_class[0], Wk.n_class[1]);
+    r1cs_open_launch<64>(ctx, "r1cs_open_rref64", L, J, Wk.n_class[0] + Wk.n_class[1], Wk.n_class[2]);
+    K16_HIP(ctx, hipGetLastError());
+    K16_HIP(ctx, hipMemcpyAsync(S.h_out, S.d_out, 3 * nc * 8, hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipMemcpyAsync(S.h_cls, S.d_cls, nw, hipMemcpyDeviceToHost, st));
+    if (emit) K16_HIP(ctx, hipMemcpyAsync(S.h_emit, S.d_emit, 64 * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    K16_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t k = 0; k < nw; k++)
+        if (S.h_cls[k] != K16_OPEN_FORCED && S.h_cls[k] != K16_OPEN_FREE && S.h_cls[k] != K16_OPEN_UNDECIDED) {
+            ctx->err = "open-set solve: the kernel left a wire without a class";
+            return K16_ERR_HIP;
+        }
+    return K16_OK;
+}
+
+extern "C" int k16_r1cs_open_system(k16_r1cs* r, const uint8_t* h_fixed, uint64_t* n_forced, uint64_t* n_free, uint64_t* n_undecided,
+                                    uint64_t* n_skipped, uint64_t* n_absent, uint64_t* n_components, uint64_t* n_dims, uint32_t* h_wires,
+                                    uint8_t* h_class, uint32_t cap, uint8_t* h_status, uint32_t* h_comp)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_forced || !n_free || !n_undecided || !n_skipped || !n_absent || !n_components || !n_dims) return K16_ERR_ARG;
+    *n_forced = *n_free = *n_undecided = *n_skipped = *n_absent = *n_components = *n_dims = 0;
+    k16_ctx* ctx = r->ctx;
+    int      rc  = r1cs_open_begin(ctx, r, h_fixed);
+    if (rc) return rc;
+    ScanOpen& S = *r->scans->open;
+    r1cs_open_build(r->scans->pairs, S.index, r->n_wires, r->M, h_fixed, (const uint64_t*)S.h_verdict.p, &S.work);
+    if ((rc = r1cs_scan_drained(ctx, r1cs_open_run(ctx, r, false, 0)))) return rc;
+    R1csOpenWork& Wk = S.work;
+    uint64_t      dims = 0;
+    for (size_t k = 0; k < Wk.comps.size(); k++) {
+        const R1csOpenComp& c = Wk.comps[k];
+        for (uint32_t j = 0; j < c.n_wires; j++) Wk.cls[Wk.wires[c.wire0 + j]] = S.h_cls[c.wire0 + j];
+        if (!c.n_cross) dims += c.n_wires - std::min<uint64_t>(S.h_out[3 * k], c.n_wires);
+    }
+    uint64_t count[6] = {0, 0, 0, 0, 0, 0}, listed = 0;
+    for (uint32_t i = 0; i < r->n_wires; i++) {
+        const uint8_t k = Wk.cls[i];
+        count[k]++;
+        if (k != K16_OPEN_FIXED && k != K16_OPEN_ABSENT && listed < cap) {
+            if (h_wires) h_wires[listed] = i;
+            if (h_class) h_class[listed] = k;
+            listed++;
+        }
+    }
+    if (h_status) memcpy(h_status, Wk.cls.data(), r->n_wires);
+    if (h_comp) memcpy(h_comp, Wk.comp.data(), (size_t)r->n_wires * 4);
+    *n_forced     = count[K16_OPEN_FORCED];
+    *n_free       = count[K16_OPEN_FREE];
+    *n_undecided  = count[K16_OPEN_UNDECIDED];
+    *n_skipped    = count[K16_OPEN_SKIPPED];
+    *n_absent     = count[K16_OPEN_ABSENT];
+    *n_components = Wk.n_components;
+    *n_dims       = dims;
+    return K16_OK;
+    });
+}
+
+extern "C" int k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint32_t wire, uint8_t* cls, uint32_t* comp_wires,
+                                       uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n, uint32_t* h_wires,
+                                       uint8_t* h_vals, uint32_t cap)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !cls || !n) return K16_ERR_ARG;
+    *cls = K16_OPEN_FIXED;
+    *n   = 0;
+    for (uint32_t* p : {comp_wires, comp_rows, comp_cross, rank})
+        if (p) *p = 0;
+    k16_ctx* ctx = r->ctx;
+    if (wire >= r->n_wires) {
+        ctx->err = "wire number out of range";
+        return K16_ERR_ARG;
+    }
+    int rc = r1cs_open_begin(ctx, r, h_fixed);
+    if (rc) return rc;
+    ScanOpen& S = *r->scans->open;
+    uint32_t  nw = 0, nr = 0, nx = 0;
+    const uint8_t host = r1cs_open_one(r->scans->pairs, S.index, r->n_wires, r->M, h_fixed, (const uint64_t*)S.h_verdict.p, wire, &S.work, &nw, &nr, &nx);
+    if (comp_wires) *comp_wires = nw;
+    if (comp_rows) *comp_rows = nr;
+    if (comp_cross) *comp_cross = nx;
+    *cls = host;
+    if (host != R1CS_OPEN_ELIMINATED) return K16_OK;
+    const R1csOpenWork& Wk  = S.work;
+    const uint32_t      col = (uint32_t)(std::lower_bound(Wk.wires.begin(), Wk.wires.end(), wire) - Wk.wires.begin());
+    *cls = K16_OPEN_FIXED;
+    if ((rc = r1cs_scan_drained(ctx, r1cs_open_run(ctx, r, true, col)))) return rc;
+    *cls = S.h_cls[col];
+    if (rank) *rank = (uint32_t)S.h_out[0];
+    if (*cls != K16_OPEN_FREE) return K16_OK;
+    uint64_t found = 0;
+    for (uint32_t j = 0; j < nw && j < 64; j++) {
+        const Fr& v = S.h_emit[j];
+        if (!(v.v[0] | v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7])) continue;
+        if (found < cap) {
+            if (h_wires) h_wires[found] = Wk.wires[j];
+            if (h_vals) memcpy(h_vals + 32 * found, v.v, 32);
+        }
+        found++;
+    }
+    *n = found;
+    return K16_OK;
     });
 }
 

@@ -50,7 +50,7 @@ SYMBOLS = [
     "k16_r1cs_check_prover_witness", "k16_r1cs_last_values", "k16_r1cs_match_zkey",
     "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences", "k16_r1cs_second_values",
     "k16_r1cs_determined_wires", "k16_r1cs_complete_witness", "k16_r1cs_complete_witness_ex", "k16_r1cs_boolean_wires",
-    "k16_r1cs_determined_wires_ex", "k16_r1cs_held_wires",
+    "k16_r1cs_determined_wires_ex", "k16_r1cs_held_wires", "k16_r1cs_open_system", "k16_r1cs_open_direction",
     "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
@@ -191,6 +191,8 @@ def load():
     L.k16_r1cs_determined_wires_ex.argtypes = [vp, vp, u32, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), vp, u32,
                                                vp, vp, vp, C.POINTER(u64), vp]
     L.k16_r1cs_held_wires.argtypes = [vp, C.POINTER(u64), vp]
+    L.k16_r1cs_open_system.argtypes = [vp, vp] + [C.POINTER(u64)] * 7 + [vp, vp, u32, vp, vp]
+    L.k16_r1cs_open_direction.argtypes = [vp, vp, u32, C.POINTER(C.c_uint8)] + [C.POINTER(u32)] * 4 + [C.POINTER(u64), vp, vp, u32]
     L.k16_prover_set_r1cs.argtypes = [vp, vp]
     L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
     L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
@@ -548,6 +550,9 @@ DET_NONE = 0xFFFFFFFF
 SOLVE_GIVEN, SOLVE_SOLVED, SOLVE_ABSENT, SOLVE_OPEN = 0, 1, 2, 3
 SOLVE_RULE_LINEAR, SOLVE_RULE_BITS = 1, 2
 DET_RULE_PIN, DET_RULE_BITS = 1, 2
+OPEN_FIXED, OPEN_ABSENT, OPEN_FORCED, OPEN_FREE, OPEN_UNDECIDED, OPEN_SKIPPED = 0, 1, 2, 3, 4, 5
+OPEN_MAX_WIRES = 64                                                         # include/k16.h K16_OPEN_MAX_WIRES
+OPEN_NO_COMPONENT = 0xFFFFFFFF
 
 
 def fullprover_set_r1cs(fullprover, r1cs_path):
@@ -832,6 +837,80 @@ class R1cs:
         full = np.zeros(self.info()["n_wires"], dtype=np.uint8) if mark else None
         self.ctx._chk(self.ctx.L.k16_r1cs_held_wires(self.h, C.byref(n), _p(full) if mark else None))
         return (int(n.value), full) if mark else int(n.value)
+
+    def _fixed_mask(self, fixed):
+        """n_wires bytes.  THE RULE: a numpy array of dtype uint8 or bool with exactly n_wires elements is a MASK (non-zero = fixed);
+        anything else -- a list, a tuple, a set, an array of any other dtype or length -- is a LIST OF WIRES.  To pass a list of
+        wires that happens to have n_wires elements, give it as a Python list or as an array of a wider integer type."""
+        n_wires = self.info()["n_wires"]
+        if isinstance(fixed, np.ndarray) and fixed.size == n_wires and fixed.dtype in (np.uint8, np.bool_):
+            return np.ascontiguousarray(fixed != 0, dtype=np.uint8)
+        mask = np.zeros(n_wires, dtype=np.uint8)
+        idx = np.array([int(s) for s in fixed], dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= n_wires):
+            raise ValueError("a fixed wire is out of range")
+        mask[idx] = 1
+        return mask
+
+    def open_system(self, fixed, cap=None, want_maps=False):
+        """k16_r1cs_open_system on the sums of the last completed check.  fixed: the wires held fixed -- a numpy array of
+        dtype uint8 or bool with exactly n_wires elements is read as a mask (non-zero = fixed), anything else as a list of wires;
+        wire 0 always is fixed.  Returns a dict: n_forced, n_free, n_undecided, n_skipped, n_absent,
+        n_components, n_dims, and wires / classes -- the lowest min(cap, ...) wires that are neither OPEN_FIXED nor OPEN_ABSENT,
+        ascending, with their OPEN_* class (cap=None asks for all).  want_maps=True adds status (the class of every wire,
+        uint8) and comp (the lowest wire of each wire's component, uint32, OPEN_NO_COMPONENT where there is none)."""
+        n_wires = self.info()["n_wires"]
+        cap = n_wires if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("cap must not be negative")
+        mask = self._fixed_mask(fixed)
+        wires, cls = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint8)
+        status = np.zeros(n_wires, dtype=np.uint8) if want_maps else None
+        comp = np.zeros(n_wires, dtype=np.uint32) if want_maps else None
+        names = ("n_forced", "n_free", "n_undecided", "n_skipped", "n_absent", "n_components", "n_dims")
+        counts = [C.c_uint64() for _ in names]
+        self.ctx._chk(self.ctx.L.k16_r1cs_open_system(self.h, _p(mask), *(C.byref(c) for c in counts), _p(wires), _p(cls), cap,
+                                                      _p(status) if want_maps else None, _p(comp) if want_maps else None))
+        out = {k: int(c.value) for k, c in zip(names, counts)}
+        k = min(cap, out["n_forced"] + out["n_free"] + out["n_undecided"] + out["n_skipped"])
+        out.update(wires=wires[:k].copy(), classes=cls[:k].copy())
+        if want_maps:
+            out.update(status=status, comp=comp)
+        return out
+
+    def open_direction(self, fixed, wire):
+        """k16_r1cs_open_direction: a dict with the wire's OPEN_* class (cls), its component's wires, LINEAR rows and CROSS
+        constraints (comp_wires, comp_rows, comp_cross), the rank, and d: {wire: value} of the canonical direction -- empty
+        unless the wire is OPEN_FREE.  Adding d to the witness leaves every unbroken constraint satisfied."""
+        mask = self._fixed_mask(fixed)
+        cls, n = C.c_uint8(), C.c_uint64()
+        nums = [C.c_uint32() for _ in range(4)]
+        wires, vals = np.zeros(OPEN_MAX_WIRES, dtype=np.uint32), np.zeros((OPEN_MAX_WIRES, 32), dtype=np.uint8)
+        self.ctx._chk(self.ctx.L.k16_r1cs_open_direction(self.h, _p(mask), int(wire), C.byref(cls), *(C.byref(x) for x in nums),
+                                                         C.byref(n), _p(wires), _p(vals), OPEN_MAX_WIRES))
+        d = {int(wires[i]): int.from_bytes(vals[i].tobytes(), "little") for i in range(min(int(n.value), OPEN_MAX_WIRES))}
+        return dict(cls=int(cls.value), comp_wires=nums[0].value, comp_rows=nums[1].value, comp_cross=nums[2].value,
+                    rank=nums[3].value, d=d)
+
+    def audit(self, seed=None, rules=None, max_passes=64):
+        """The closure and the open-set solve in turns, until the solve forces nothing more: each pass runs the closure
+        (determined_wires with `rules`) on the seed, holds fixed what is not DET_OPEN, runs open_system, and adds the FORCED wires
+        to the seed -- they are forced given the fixed ones, so the next closure may start from them.  Returns (classes, forced_in,
+        passes): the OPEN_* class of every wire after the last pass (a wire forced in an earlier pass is OPEN_FIXED there),
+        the pass (1, 2, ...) in which open_system forced each wire (0: never), and the number of passes."""
+        n_wires = self.info()["n_wires"]
+        forced_in = np.zeros(n_wires, dtype=np.uint32)
+        for n_pass in range(1, int(max_passes) + 1):
+            status = self.determined_wires(seed, cap=0, want_maps=True, rules=rules)[5]
+            if seed is None:                                     # the closure's default seed: what this run called DET_SEED
+                seed = np.nonzero(status == DET_SEED)[0].tolist()
+            res = self.open_system(status != DET_OPEN, cap=0, want_maps=True)
+            forced = np.nonzero(res["status"] == OPEN_FORCED)[0]
+            if forced.size == 0:
+                return res["status"], forced_in, n_pass
+            forced_in[forced] = n_pass
+            seed = sorted({int(x) for x in seed} | set(forced.tolist()))
+        raise RuntimeError("audit: open_system still forces wires after %d passes" % max_passes)
 
     def boolean_wires(self, mark=False):
         """k16_r1cs_boolean_wires: the number of wires some constraint of the circuit holds to {0, 1}; mark=True: (n, ndarray of
