@@ -873,6 +873,30 @@ int  k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint32_t wire,
                              uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n, uint32_t* h_wires,
                              uint8_t* h_vals /* 32 B each */, uint32_t cap);
 
+/* ---- the open-set solve with a wider cap: components of up to K16_OPEN_MAX_WIRES_EX wires ----
+ * One multiplication between two hints glues their components together, and a component of more than K16_OPEN_MAX_WIRES wires is
+ * SKIPPED by the calls above whatever its FORCED wires would be.  The _ex calls take the cap as an argument:
+ *   max_wires   64 .. K16_OPEN_MAX_WIRES_EX.  Anything else is K16_ERR_ARG before anything is launched or written: every output
+ *               keeps its bytes and the object keeps its check.  A component of more than max_wires wires is SKIPPED.
+ * Definitions, classes, the canonical direction, preconditions, errors and threading are those of k16_r1cs_open_system and
+ * k16_r1cs_open_direction, with "K16_OPEN_MAX_WIRES" read as max_wires; the remaining arguments are theirs, in their order.
+ * max_wires == 64 runs their code and allocates nothing beyond it: every output byte is theirs (the convention of
+ * k16_r1cs_determined_wires_ex).  k16_r1cs_open_direction_ex returns up to *comp_wires <= max_wires non-zeros; cap works as above.
+ * The first call with max_wires > 64 adds, once per object, an arena of 144 MiB on the device (K16_ERR_NOMEM when the device has
+ * not got it, as every other stage; the object and the 64-wire calls stay usable).  Components of 65 .. 128 and 129 .. 256 wires
+ * are two more size classes, eliminated by k_r1cs_open_rref_wide: one workgroup of 128 / 256 threads per component, thread j
+ * owning column j, the basis in a slab of the arena per workgroup (256 / 64 workgroups a launch, striding the components), a
+ * fraction-free elimination -- no field inversion in k16_r1cs_open_system_ex; in k16_r1cs_open_direction_ex every pivot's thread
+ * inverts its own pivot value at the same time (csrc/r1cs_scan.hip). */
+#define K16_OPEN_MAX_WIRES_EX 256
+int  k16_r1cs_open_system_ex(k16_r1cs* r, const uint8_t* h_fixed, uint32_t max_wires, uint64_t* n_forced, uint64_t* n_free,
+                             uint64_t* n_undecided, uint64_t* n_skipped, uint64_t* n_absent, uint64_t* n_components, uint64_t* n_dims,
+                             uint32_t* h_wires, uint8_t* h_class, uint32_t cap, uint8_t* h_status /* n_wires bytes, may be NULL */,
+                             uint32_t* h_comp /* n_wires words, may be NULL */);
+int  k16_r1cs_open_direction_ex(k16_r1cs* r, const uint8_t* h_fixed, uint32_t max_wires, uint32_t wire, uint8_t* cls,
+                                uint32_t* comp_wires, uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n,
+                                uint32_t* h_wires, uint8_t* h_vals /* 32 B each */, uint32_t cap);
+
 /* ---- checked proving: every prove call carries the list of the constraints its witness breaks ----
  * k16_prover_set_r1cs attaches a circuit to a prover (NULL detaches; not owned, as k16_prover_set_vk: destroy it after the
  * prover, or detach first).  K16_ERR_ARG unless r lives on the prover's context, its nWires is the key's nVars and its number of

@@ -12,6 +12,9 @@
 // A component of at most R1CS_OPEN_MAX_WIRES wires is ELIMINATED: the work list holds its wires, ascending -- the columns of its
 // matrix -- and a CSR of its LINEAR rows, ascending by constraint, each entry (column, incidence).  The components are grouped
 // by size class (<= 16, <= 32, <= 64 wires: one launch each) and ordered by id inside a class.  A larger component is SKIPPED.
+// The builder and the walk from one wire take the cap as `max_wires`, R1CS_OPEN_MAX_WIRES .. R1CS_OPEN_MAX_WIRES_EX: two more
+// classes (<= 128, <= 256 wires: k_r1cs_open_rref_wide) follow the three, in the same layout; with the
+// cap at R1CS_OPEN_MAX_WIRES they are empty and the work list is byte for byte what it was without them.
 // Everything here is one linear walk over the outside wires' incidences; nothing iterates to a fixed point except the
 // union-find's path halving.
 #pragma once
@@ -20,9 +23,11 @@
 
 namespace k16 {
 
-constexpr uint32_t R1CS_OPEN_MAX_WIRES = 64;
-constexpr uint32_t R1CS_OPEN_CLASSES   = 3;
-constexpr uint32_t R1CS_OPEN_NONE      = 0xffffffffu;
+constexpr uint32_t R1CS_OPEN_MAX_WIRES    = 64;
+constexpr uint32_t R1CS_OPEN_MAX_WIRES_EX = 256;
+constexpr uint32_t R1CS_OPEN_NARROW       = 3; // the classes of one wave: <= 16, <= 32, <= 64 wires
+constexpr uint32_t R1CS_OPEN_CLASSES      = 5; // and the wide ones: <= 128, <= 256 wires
+constexpr uint32_t R1CS_OPEN_NONE         = 0xffffffffu;
 constexpr uint32_t r1cs_open_class_wires(uint32_t k) { return 16u << k; }
 
 // what the host alone decides of a wire's class; ELIMINATED wires get theirs from the kernel
@@ -62,7 +67,7 @@ struct R1csOpenWork {
     std::vector<uint8_t>       cls;        // [n_wires]: R1CS_OPEN_FIXED / _ABSENT / _ELIMINATED / _SKIPPED
     std::vector<uint32_t>      comp;       // [n_wires]: the component's id, R1CS_OPEN_NONE for FIXED / ABSENT
     std::vector<R1csOpenComp>  comps;      // the eliminated components, by size class, then by id
-    uint32_t                   n_class[R1CS_OPEN_CLASSES] = {0, 0, 0};
+    uint32_t                   n_class[R1CS_OPEN_CLASSES] = {0, 0, 0, 0, 0};
     std::vector<uint32_t>      wires;      // the eliminated components' wires
     std::vector<uint32_t>      row;        // the constraint of every row
     std::vector<uint32_t>      row_start;  // [rows + 1]
@@ -89,18 +94,18 @@ inline uint8_t r1cs_open_kind(const R1csPairs& P, const R1csOpenIndex& X, const 
 
 namespace r1cs_open_detail {
 
-// Slots for the components in `ids` (ascending) of at most R1CS_OPEN_MAX_WIRES wires, grouped by size class; their wires, rows
-// and entries.  size[id]: the component's wires; comp[w]: the id of wire w's component; slot: scratch, n_wires words.
+// Slots for the components in `ids` (ascending) of at most max_wires wires, grouped by size class; their wires, rows and
+// entries.  size[id]: the component's wires; comp[w]: the id of wire w's component; slot: scratch, n_wires words.
 inline void fill(const R1csPairs& P, const R1csOpenIndex& X, const uint8_t* fixed, const std::vector<uint32_t>& ids,
                  const std::vector<uint32_t>& size, const std::vector<uint32_t>& members, const std::vector<uint32_t>& rows,
-                 std::vector<uint32_t>& slot, R1csOpenWork* W)
+                 std::vector<uint32_t>& slot, uint32_t max_wires, R1csOpenWork* W)
 {
     const uint32_t skip = P.start[1];
     // slots by class, then by id
     for (uint32_t k = 0; k < R1CS_OPEN_CLASSES; k++)
         for (uint32_t id : ids) {
             const uint32_t n = size[id];
-            if (n > r1cs_open_class_wires(k) || (k && n <= r1cs_open_class_wires(k - 1))) continue;
+            if (n > max_wires || n > r1cs_open_class_wires(k) || (k && n <= r1cs_open_class_wires(k - 1))) continue;
             slot[id] = (uint32_t)W->comps.size();
             W->comps.push_back(R1csOpenComp{0, 0, 0, 0, 0, id});
             W->n_class[k]++;
@@ -184,9 +189,10 @@ inline void fill(const R1csPairs& P, const R1csOpenIndex& X, const uint8_t* fixe
 
 } // namespace r1cs_open_detail
 
-// Every component of the circuit.  fixed: n_wires bytes, non-zero = held fixed; verdict: the check's mask.
+// Every component of the circuit.  fixed: n_wires bytes, non-zero = held fixed; verdict: the check's mask; max_wires: the cap,
+// R1CS_OPEN_MAX_WIRES .. R1CS_OPEN_MAX_WIRES_EX (the callers check it).
 inline void r1cs_open_build(const R1csPairs& P, const R1csOpenIndex& X, uint32_t n_wires, uint32_t M, const uint8_t* fixed,
-                            const uint64_t* verdict, R1csOpenWork* W)
+                            const uint64_t* verdict, R1csOpenWork* W, uint32_t max_wires = R1CS_OPEN_MAX_WIRES)
 {
     *W = R1csOpenWork();
     W->kind.assign(M, R1CS_KIND_NONE);
@@ -244,11 +250,11 @@ inline void r1cs_open_build(const R1csPairs& P, const R1csOpenIndex& X, uint32_t
     }
     W->n_components = ids.size();
     for (uint32_t w : members) {
-        const bool skipped = size[W->comp[w]] > R1CS_OPEN_MAX_WIRES;
+        const bool skipped = size[W->comp[w]] > max_wires;
         W->cls[w]          = skipped ? R1CS_OPEN_SKIPPED : R1CS_OPEN_ELIMINATED;
         W->n_skipped += skipped;
     }
-    r1cs_open_detail::fill(P, X, fixed, ids, size, members, rows, parent, W); // (parent serves as the slot table from here on)
+    r1cs_open_detail::fill(P, X, fixed, ids, size, members, rows, parent, max_wires, W); // (parent serves as the slot table from here on)
 }
 
 // The component of ONE outside wire, by a walk from it: the same work list with that component alone (none when it is SKIPPED).
@@ -256,7 +262,7 @@ inline void r1cs_open_build(const R1csPairs& P, const R1csOpenIndex& X, uint32_t
 // the wire's host class (R1CS_OPEN_FIXED and _ABSENT: no component, the counts are 0).
 inline uint8_t r1cs_open_one(const R1csPairs& P, const R1csOpenIndex& X, uint32_t n_wires, uint32_t M, const uint8_t* fixed,
                              const uint64_t* verdict, uint32_t wire, R1csOpenWork* W, uint32_t* n_wires_out, uint32_t* n_rows_out,
-                             uint32_t* n_cross_out)
+                             uint32_t* n_cross_out, uint32_t max_wires = R1CS_OPEN_MAX_WIRES)
 {
     *W = R1csOpenWork();
     *n_wires_out = *n_rows_out = *n_cross_out = 0;
@@ -289,7 +295,7 @@ inline uint8_t r1cs_open_one(const R1csPairs& P, const R1csOpenIndex& X, uint32_
     const uint32_t id = members[0];
     *n_wires_out      = (uint32_t)members.size();
     for (uint32_t c : rows) (W->kind[c] == R1CS_KIND_CROSS ? *n_cross_out : *n_rows_out)++;
-    const bool skipped = members.size() > R1CS_OPEN_MAX_WIRES;
+    const bool skipped = members.size() > max_wires;
     for (uint32_t w : members) {
         W->comp[w] = id;
         W->cls[w]  = skipped ? R1CS_OPEN_SKIPPED : R1CS_OPEN_ELIMINATED;
@@ -301,7 +307,7 @@ inline uint8_t r1cs_open_one(const R1csPairs& P, const R1csOpenIndex& X, uint32_
     }
     std::vector<uint32_t> size(n_wires, 0), slot(n_wires, 0);
     size[id] = (uint32_t)members.size();
-    r1cs_open_detail::fill(P, X, fixed, std::vector<uint32_t>{id}, size, members, rows, slot, W);
+    r1cs_open_detail::fill(P, X, fixed, std::vector<uint32_t>{id}, size, members, rows, slot, max_wires, W);
     return R1CS_OPEN_ELIMINATED;
 }
 

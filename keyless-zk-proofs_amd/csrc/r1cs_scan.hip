@@ -1122,7 +1122,234 @@ __global__ void __launch_bounds__(64) k_r1cs_open_rref(const IncList L, const Op
     }
 }
 
-// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Nine stages, each made whole by the first call
+// The wide classes of the open-set solve (k16_r1cs_open_system_ex / k16_r1cs_open_direction_ex with max_wires > 64; DESIGN.md
+// section 10i): components of 65 .. 128 and 129 .. 256 wires.  Definitions, work list, scalings and operand bounds are those of
+// k_r1cs_open_rref above.  ONE WORKGROUP of W threads (W / 64 waves) per component, thread j owning column j; a workgroup
+// strides the components of its class.
+//   the basis      in a global slab per WORKGROUP, slab[(row * 9 + limb) * W + column], W * 9 * W words.  A thread reads and
+//                  writes ITS OWN COLUMN of the slab and nothing else, so no store of one wave is ever read by another through
+//                  global memory; what crosses threads goes through LDS between workgroup barriers.  A slab row is written in
+//                  all W columns when it is inserted, before anything reads it: nothing is zeroed between components
+//   fraction-free  the basis rows are REDUCED BUT NOT NORMALISED: row b holds some p_b != 0 in its own pivot column c_b and 0
+//                  in every other pivot column, so basis_b = p_b R_b for the row R_b of the reduced row echelon form.  A row v
+//                  of J is reduced by cross-multiplication, v <- p_b v - v[c_b] basis_b, for the pivot columns among the row's
+//                  OWN ENTRIES only (a column the row has no entry in holds an exact zero and stays zero: basis_b is 0 in the
+//                  other pivot columns).  v[c_b] at the time of the step is the row's ORIGINAL entry (from LDS) times the
+//                  product P of the p_b of the steps before it, which every thread carries redundantly: no step waits for
+//                  another and the loop over the entries holds no barrier.  A remainder that is zero mod r in every non-pivot
+//                  column (fr9_nonzero on lazy representatives) is discarded.  Else the lowest non-zero column p (ballot per
+//                  wave, minimum over the waves through LDS) becomes a pivot with s = v[p]: basis_b <- s basis_b - basis_b[p] v
+//                  for the rows with basis_b[p] != 0 (a factor whose words are all zero skips its row: nothing to clear, and
+//                  no scaling is owed), which lifts p_b to s p_b; the remainder is inserted as it is, p_rank = s.  Scaling a
+//                  row by a non-zero value changes no zero pattern: pivots are leading entries as above, and pivots, rank,
+//                  the FORCED mask and the class bytes are those of the reduced row echelon form.  NO INVERSION.
+//   through LDS    the row (rowv) and the columns of its entries (ecol), the basis row of a pivot column (rowof), the pivot
+//                  values (pval: written by the thread of the pivot column, which holds p_b in its own column), the new pivot's
+//                  column of the basis rows (fcol: thread p gathers it from its own column), the waves' lowest live columns
+//                  (wmin), the rows with a non-zero free column (busy), what thread emit_col knows of its column (info), and
+//                  per basis row a mask of the columns that hold a non-zero word (nzm: a ballot per wave whenever the row is
+//                  stored; it may name a column whose value is zero mod r, never miss one that is not), from which the rows a
+//                  new pivot's column has to be cleared from are listed (hitm): thread p gathers those rows only
+//   no hangs       every loop bound is a count the host wrote (components, rows, entries) or the rank, which grows by one per
+//                  inserted row and cannot pass W; every __syncthreads() sits in control flow that is uniform over the
+//                  workgroup -- "this row is in the row space, skip it" is decided from wmin, which every thread reads after a
+//                  barrier, never per wave; every index read from the work list is clamped as in k_r1cs_open_rref, so a wrong
+//                  list reads and writes nothing outside a buffer
+// out: 9 words per component, rank | pivot mask [4] | FORCED mask [4].  With `emit` (one component) the canonical direction of
+// column emit_col is written as W values: every pivot thread inverts ITS OWN pivot value, all at once (one inversion's latency,
+// whatever the rank), v_f[p] = -basis[row(p)][f] / p_row(p) with basis[.][f] gathered by thread f through LDS; where emit_col
+// is a pivot its thread runs one more inversion, broadcast through LDS.
+template <uint32_t W>
+__global__ void __launch_bounds__(W) k_r1cs_open_rref_wide(const IncList L, const OpenJob J, uint32_t* __restrict__ slabs)
+{
+    constexpr uint32_t WAVES = W / 64u, NONE = 0xffffffffu;
+    __shared__ uint32_t rowv[9 * W]; // [limb * W + column]
+    __shared__ uint32_t fcol[9 * W]; // [row * 9 + limb]: basis[row][p] of the pivot p being inserted (emit: of column f)
+    __shared__ uint32_t pval[9 * W]; // [row * 9 + limb]: p_b
+    __shared__ uint32_t sval[9];
+    __shared__ uint32_t ecol[W];     // the columns of the row's entries, NONE where the list names none
+    __shared__ uint32_t rowof[W];    // the basis row of a pivot column, NONE for a free one
+    __shared__ uint32_t busy[W];     // != 0: basis row b has a non-zero free column
+    __shared__ uint32_t wmin[WAVES];
+    __shared__ uint32_t info[3];
+    __shared__ unsigned long long nzm[W * WAVES]; // [row * WAVES + wave]: bit l -- column 64 wave + l of the row holds a non-zero word
+    __shared__ unsigned long long hitm[WAVES];    // bit b: basis row b has such a word in the column of the new pivot
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t* const slab = slabs + (size_t)blockIdx.x * (W * 9u * W) + tid; // this thread's column
+    auto load_own = [&](uint32_t row) {
+        Fr9 b;
+#pragma unroll
+        for (int i = 0; i < 9; i++) b.l[i] = slab[(row * 9u + i) * W];
+        return b;
+    };
+    auto store_own = [&](uint32_t row, const Fr9& b) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) slab[(row * 9u + i) * W] = b.l[i];
+    };
+    auto store_marked = [&](uint32_t row, const Fr9& b) { // by every thread of the workgroup: the row's mask follows its words
+        store_own(row, b);
+        const unsigned long long m = __ballot((b.l[0] | b.l[1] | b.l[2] | b.l[3] | b.l[4] | b.l[5] | b.l[6] | b.l[7] | b.l[8]) != 0);
+        if (lane == 0) nzm[row * WAVES + wave] = m;
+    };
+    auto marked = [&](uint32_t row, uint32_t column) { return (nzm[row * WAVES + (column >> 6)] >> (column & 63u)) & 1ull; };
+    auto load_lds = [&](const uint32_t* at, uint32_t stride) {
+        Fr9 b;
+#pragma unroll
+        for (int i = 0; i < 9; i++) b.l[i] = at[i * stride];
+        return b;
+    };
+    // the lowest thread with `live`, NONE when there is none: the same value in every thread.  Two barriers, uniform.
+    auto lowest = [&](bool live) {
+        const unsigned long long m = __ballot(live);
+        __syncthreads(); // (wmin is read by now)
+        if (lane == 0) wmin[wave] = m ? 64u * wave + (uint32_t)__ffsll((long long)m) - 1u : NONE;
+        __syncthreads();
+        uint32_t p = NONE;
+#pragma unroll
+        for (uint32_t i = 0; i < WAVES; i++) p = min(p, wmin[i]);
+        return p;
+    };
+    for (uint32_t k = blockIdx.x; k < J.n_comp; k += gridDim.x) {
+        const R1csOpenComp C  = J.comp[k];
+        const uint32_t     nw = min(C.n_wires, W);
+        const bool         col = tid < nw;
+        uint32_t           rank = 0, my_row = 0; // my_row: the basis row of this thread's column, where it is a pivot
+        bool               pivot = false;
+        rowof[tid] = NONE; // (the component before is done with it: the barriers of its FORCED pass lie between)
+        for (uint32_t r = 0; r < C.n_rows; r++) {
+            if (C.row0 + r >= J.n_rows) break; // (the same in every thread)
+            const uint32_t rs = J.row_start[C.row0 + r], re = min(J.row_start[C.row0 + r + 1], J.n_ent);
+            const uint32_t len = re > rs ? min(re - rs, W) : 0;
+            __syncthreads(); // (the row before is read by now)
+#pragma unroll
+            for (int i = 0; i < 9; i++) rowv[i * W + tid] = 0;
+            ecol[tid] = NONE;
+            __syncthreads();
+            if (tid < len) {
+                const uint2 e = J.ent[rs + tid];
+                if (e.x < nw && e.y < L.n_pairs) {
+                    const IncTerms t = inc_terms(L.inc[e.y], L);
+#pragma unroll
+                    for (int i = 0; i < 9; i++) rowv[i * W + e.x] = t.lin.l[i];
+                    ecol[tid] = e.x;
+                }
+            }
+            __syncthreads();
+            Fr9  v = load_lds(&rowv[tid], W), P = fr9_one();
+            bool first = true; // (P is 1: the first step multiplies nothing by it)
+            for (uint32_t e = 0; e < len; e++) { // every condition below is the same in every thread: read from LDS
+                const uint32_t c = ecol[e];
+                if (c >= W) continue;
+                const uint32_t b = rowof[c];
+                if (b >= rank) continue; // a free column
+                const Fr9 o = load_lds(&rowv[c], W), pb = load_lds(&pval[b * 9u], 1);
+                const Fr9 f = first ? o : frmul9(o, P);
+                v     = frsub9(frmul9(pb, v), frmul9(f, load_own(b)));
+                P     = first ? pb : frmul9(P, pb);
+                first = false;
+            }
+            const uint32_t p = lowest(col && !pivot && fr9_nonzero(v));
+            if (p == NONE || rank >= W) continue; // in the row space already: every thread read the same wmin
+            const unsigned long long hit = __ballot(tid < rank && marked(tid, p)); // the rows column p may have to be cleared from
+            if (lane == 0) hitm[wave] = hit;
+            __syncthreads();
+            if (tid == p) {
+#pragma unroll
+                for (int i = 0; i < 9; i++) sval[i] = pval[rank * 9u + i] = v.l[i];
+                for (uint32_t wv = 0; wv < WAVES; wv++)
+                    for (unsigned long long m = hitm[wv]; m; m &= m - 1) {
+                        const uint32_t b = 64u * wv + (uint32_t)__ffsll((long long)m) - 1u;
+                        const Fr9      f = load_own(b);
+#pragma unroll
+                        for (int i = 0; i < 9; i++) fcol[b * 9u + i] = f.l[i];
+                    }
+                rowof[p] = rank;
+                pivot    = true;
+                my_row   = rank;
+            }
+            __syncthreads();
+            const Fr9 s = load_lds(sval, 1);
+            for (uint32_t wv = 0; wv < WAVES; wv++)
+                for (unsigned long long m = hitm[wv]; m; m &= m - 1) { // (every thread alike: hitm and fcol are read from LDS)
+                    const uint32_t b = 64u * wv + (uint32_t)__ffsll((long long)m) - 1u;
+                    const Fr9      f = load_lds(&fcol[b * 9u], 1);
+                    if (!(f.l[0] | f.l[1] | f.l[2] | f.l[3] | f.l[4] | f.l[5] | f.l[6] | f.l[7] | f.l[8])) continue;
+                    const Fr9 c = frsub9(frmul9(s, load_own(b)), frmul9(f, v));
+                    store_marked(b, c);
+                    if (pivot && my_row == b && tid != p) { // this thread's column holds p_b: s p_b now
+#pragma unroll
+                        for (int i = 0; i < 9; i++) pval[b * 9u + i] = c.l[i];
+                    }
+                }
+            store_marked(rank, v);
+            rank++;
+        }
+        // FORCED: a pivot whose row is zero in every free column
+        __syncthreads();
+        busy[tid] = 0;
+        __syncthreads();
+        if (col && !pivot)
+            for (uint32_t b = 0; b < rank; b++)
+                if (marked(b, tid) && fr9_nonzero(load_own(b))) busy[b] = 1; // (every writer writes the same word)
+        __syncthreads();
+        const bool               forced = pivot && !busy[my_row];
+        const unsigned long long pm = __ballot(pivot), fm = __ballot(forced);
+        unsigned long long*      out = J.out + 9 * (size_t)k;
+        if (lane == 0) {
+            out[1 + wave] = pm;
+            out[5 + wave] = fm;
+        }
+        if (tid == 0) {
+            out[0] = rank;
+            for (uint32_t i = WAVES; i < 4; i++) out[1 + i] = out[5 + i] = 0;
+        }
+        if (col && (uint64_t)C.wire0 + tid < J.n_wires)
+            J.cls[C.wire0 + tid] = (uint8_t)(forced ? K16_OPEN_FORCED : C.n_cross ? K16_OPEN_UNDECIDED : K16_OPEN_FREE);
+        if (J.emit) {
+            const uint32_t x = min(J.emit_col, W - 1u);
+            if (tid == x) {
+                info[0] = pivot;
+                info[1] = forced;
+                info[2] = my_row;
+            }
+            __syncthreads();
+            const bool     on_pivot = info[0] != 0;
+            const uint32_t row      = min(info[2], W - 1u);
+            bool           have     = x < nw && !info[1];
+            uint32_t       f        = x;
+            if (on_pivot) { // (the same branch in every thread) the lowest free column in x's row
+                f    = lowest(col && !pivot && row < rank && fr9_nonzero(load_own(row < rank ? row : 0u)));
+                have = have && f != NONE;
+            }
+            Fr9 d = fq9_zero();
+            if (have) { // (the same branch in every thread)
+                if (tid == f)
+                    for (uint32_t b = 0; b < rank; b++) {
+                        const Fr9 t = marked(b, tid) ? load_own(b) : fq9_zero();
+#pragma unroll
+                        for (int i = 0; i < 9; i++) fcol[b * 9u + i] = t.l[i];
+                    }
+                Fr9 inv = fq9_zero();
+                if (pivot) inv = frinv9(load_own(my_row)); // its own pivot value: every pivot thread at once
+                __syncthreads();
+                if (tid == f) d = fr9_one();
+                else if (pivot) d = frmul9(frsub9(fq9_zero(), load_lds(&fcol[my_row * 9u], 1)), inv);
+                if (on_pivot) {
+                    if (tid == x) {
+                        const Fr9 t = frinv9(d);
+#pragma unroll
+                        for (int i = 0; i < 9; i++) sval[i] = t.l[i];
+                    }
+                    __syncthreads();
+                    d = frmul9(d, load_lds(sval, 1));
+                }
+            }
+            st_fr(&J.emit[tid], fr9_to_standard(d));
+        }
+    }
+}
+
+// ---- what the diagnostics keep on the object (r1cs_obj.h: k16_r1cs::scans).  Ten stages, each made whole by the first call
 // that needs it and kept until the object goes; a stage is ready when its pointer is set.
 struct ScanList { // the list on the device, and the unbound-wire scan's mask
     DevBuf<uint4>                 inc;     // R1csPair of every incidence of the wires 1 .. n_wires - 1
@@ -1191,6 +1418,13 @@ struct ScanOpen { // the open-set solve: every size is bounded by the circuit's,
     DevBuf<Fr>                    d_emit;    // [64] a direction
     PinnedBuf<Fr>                 h_emit;
 };
+struct ScanOpenWide { // the wide classes of the open-set solve: by the first call with max_wires > 64, beside ScanOpen
+    DevBuf<uint32_t>              d_arena;   // OPEN_WIDE_ARENA bytes: the basis slabs of the workgroups of one launch
+    DevBuf<unsigned long long>    d_out;     // [9 (n_wires / 65 + 1)] rank | pivot mask [4] | FORCED mask [4] of every wide component
+    PinnedBuf<unsigned long long> h_out;
+    DevBuf<Fr>                    d_emit;    // [256] a direction
+    PinnedBuf<Fr>                 h_emit;
+};
 
 } // namespace
 
@@ -1205,6 +1439,7 @@ struct k16::R1csScans {
     std::unique_ptr<ScanBits>   bits;
     std::unique_ptr<ScanHeld>   held;
     std::unique_ptr<ScanOpen>   open;
+    std::unique_ptr<ScanOpenWide> open_wide;
 };
 void k16::r1cs_scans_delete(R1csScans* s) { delete s; }
 
@@ -2146,14 +2381,59 @@ static void r1cs_open_launch(k16_ctx* ctx, const char* name, const IncList& L, O
     hipLaunchKernelGGL(k_r1cs_open_rref<W>, dim3(std::min(n, OPEN_GRID)), dim3(64), 0, ctx->stream, L, J);
 }
 
+// The wide classes.  One arena of basis slabs, shared by both (their launches follow each other on the stream): 144 MiB =
+// 256 slabs of 128 x 9 x 128 words (0.5625 MiB: one workgroup of 2 waves on each of the chip's 256 CUs) = 64 slabs of
+// 256 x 9 x 256 words (2.25 MiB: one workgroup of 4 waves on a quarter of the CUs).  The grid of a launch never passes the
+// slabs: a workgroup strides the components of its class.
+constexpr size_t OPEN_WIDE_ARENA = (size_t)144 << 20;
+template <uint32_t W>
+constexpr uint32_t open_wide_grid() { return (uint32_t)(OPEN_WIDE_ARENA / ((size_t)W * 9 * W * 4)); }
+static_assert(open_wide_grid<128>() == 256 && open_wide_grid<256>() == 64, "the arena is cut into whole slabs");
+
+static int r1cs_open_wide_alloc(k16_ctx* ctx, k16_r1cs* r, ScanOpenWide& S)
+{
+    const size_t n_out = 9 * ((size_t)r->n_wires / (R1CS_OPEN_MAX_WIRES + 1) + 1) * 8;
+    int          rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_arena, OPEN_WIDE_ARENA))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_out, n_out))) return rc;
+    if ((rc = r1cs_scan_alloc(ctx, S.d_emit, R1CS_OPEN_MAX_WIRES_EX * sizeof(Fr)))) return rc;
+    K16_HIP(ctx, S.h_out.alloc(n_out));
+    K16_HIP(ctx, S.h_emit.alloc(R1CS_OPEN_MAX_WIRES_EX * sizeof(Fr)));
+    return K16_OK;
+}
+
+template <uint32_t W>
+static void r1cs_open_launch_wide(k16_ctx* ctx, const char* name, const IncList& L, OpenJob J, const ScanOpenWide& Sw, uint32_t first,
+                                  uint32_t first_wide, uint32_t n)
+{
+    if (!n) return;
+    J.comp += first;
+    J.out = Sw.d_out.p + 9 * (size_t)first_wide;
+    J.n_comp = n;
+    if (J.emit) J.emit = Sw.d_emit.p;
+    k16_stat_scope sc(ctx, name, ctx->stream);
+    hipLaunchKernelGGL(k_r1cs_open_rref_wide<W>, dim3(std::min(n, open_wide_grid<W>())), dim3(W), 0, ctx->stream, L, J, Sw.d_arena.p);
+}
+
+// What the last run left for component k of the work list: its rank, and the direction the emit path wrote.
+static uint64_t r1cs_open_rank(const k16_r1cs* r, size_t k)
+{
+    const R1csOpenWork& Wk     = r->scans->open->work;
+    const size_t        narrow = (size_t)Wk.n_class[0] + Wk.n_class[1] + Wk.n_class[2];
+    return k < narrow ? r->scans->open->h_out[3 * k] : r->scans->open_wide->h_out[9 * (k - narrow)];
+}
+
 // The work list up, one launch per size class, ranks, masks and classes (and the direction of column emit_col, where asked) down.
+// The wide classes are empty unless the list was built with a cap above R1CS_OPEN_MAX_WIRES, and then the wide stage is there.
 static int r1cs_open_run(k16_ctx* ctx, k16_r1cs* r, bool emit, uint32_t emit_col)
 {
     const ScanOpen&     S  = *r->scans->open;
     const R1csOpenWork& Wk = S.work;
     const size_t        nc = Wk.comps.size(), nw = Wk.wires.size(), nr = Wk.row.size(), ne = Wk.ent.size();
     if (!nc) return K16_OK;
-    if (nc > r->n_wires || nw > r->n_wires || nr > r->M || ne > r1cs_walked(r->scans->pairs)) {
+    const uint32_t narrow = Wk.n_class[0] + Wk.n_class[1] + Wk.n_class[2], wide = Wk.n_class[3] + Wk.n_class[4];
+    if (nc > r->n_wires || nw > r->n_wires || nr > r->M || ne > r1cs_walked(r->scans->pairs) || (size_t)narrow + wide != nc ||
+        (wide && (!r->scans->open_wide || wide > r->n_wires / (R1CS_OPEN_MAX_WIRES + 1)))) {
         ctx->err = "open-set solve: the work list outgrew the circuit";
         return K16_ERR_HIP;
     }
@@ -2170,10 +2450,20 @@ static int r1cs_open_run(k16_ctx* ctx, k16_r1cs* r, bool emit, uint32_t emit_col
     r1cs_open_launch<16>(ctx, "r1cs_open_rref16", L, J, 0, Wk.n_class[0]);
     r1cs_open_launch<32>(ctx, "r1cs_open_rref32", L, J, Wk.n_class[0], Wk.n_class[1]);
     r1cs_open_launch<64>(ctx, "r1cs_open_rref64", L, J, Wk.n_class[0] + Wk.n_class[1], Wk.n_class[2]);
+    if (wide) {
+        const ScanOpenWide& Sw = *r->scans->open_wide;
+        r1cs_open_launch_wide<128>(ctx, "r1cs_open_rref128", L, J, Sw, narrow, 0, Wk.n_class[3]);
+        r1cs_open_launch_wide<256>(ctx, "r1cs_open_rref256", L, J, Sw, narrow + Wk.n_class[3], Wk.n_class[3], Wk.n_class[4]);
+    }
     K16_HIP(ctx, hipGetLastError());
-    K16_HIP(ctx, hipMemcpyAsync(S.h_out, S.d_out, 3 * nc * 8, hipMemcpyDeviceToHost, st));
+    if (narrow) K16_HIP(ctx, hipMemcpyAsync(S.h_out, S.d_out, 3 * (size_t)narrow * 8, hipMemcpyDeviceToHost, st));
     K16_HIP(ctx, hipMemcpyAsync(S.h_cls, S.d_cls, nw, hipMemcpyDeviceToHost, st));
-    if (emit) K16_HIP(ctx, hipMemcpyAsync(S.h_emit, S.d_emit, 64 * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    if (emit && narrow) K16_HIP(ctx, hipMemcpyAsync(S.h_emit, S.d_emit, 64 * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    if (wide) {
+        const ScanOpenWide& Sw = *r->scans->open_wide;
+        K16_HIP(ctx, hipMemcpyAsync(Sw.h_out, Sw.d_out, 9 * (size_t)wide * 8, hipMemcpyDeviceToHost, st));
+        if (emit) K16_HIP(ctx, hipMemcpyAsync(Sw.h_emit, Sw.d_emit, R1CS_OPEN_MAX_WIRES_EX * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    }
     K16_HIP(ctx, hipStreamSynchronize(st));
     for (size_t k = 0; k < nw; k++)
         if (S.h_cls[k] != K16_OPEN_FORCED && S.h_cls[k] != K16_OPEN_FREE && S.h_cls[k] != K16_OPEN_UNDECIDED) {
@@ -2183,25 +2473,40 @@ static int r1cs_open_run(k16_ctx* ctx, k16_r1cs* r, bool emit, uint32_t emit_col
     return K16_OK;
 }
 
-extern "C" int k16_r1cs_open_system(k16_r1cs* r, const uint8_t* h_fixed, uint64_t* n_forced, uint64_t* n_free, uint64_t* n_undecided,
-                                    uint64_t* n_skipped, uint64_t* n_absent, uint64_t* n_components, uint64_t* n_dims, uint32_t* h_wires,
-                                    uint8_t* h_class, uint32_t cap, uint8_t* h_status, uint32_t* h_comp)
+// The cap of an _ex call, judged before anything is launched or written.
+static int r1cs_open_cap(k16_ctx* ctx, uint32_t max_wires)
 {
-    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
-    if (!r || !n_forced || !n_free || !n_undecided || !n_skipped || !n_absent || !n_components || !n_dims) return K16_ERR_ARG;
+    if (max_wires < R1CS_OPEN_MAX_WIRES || max_wires > R1CS_OPEN_MAX_WIRES_EX) {
+        ctx->err = "open-set solve: max_wires outside 64 .. 256";
+        return K16_ERR_ARG;
+    }
+    return K16_OK;
+}
+// The wide stage, where the cap asks for it: made by the first such call.
+static int r1cs_open_wide_stage(k16_ctx* ctx, k16_r1cs* r, uint32_t max_wires)
+{
+    if (max_wires <= R1CS_OPEN_MAX_WIRES) return K16_OK;
+    return r1cs_scan_stage(ctx, r->scans->open_wide, [&](ScanOpenWide& S) { return r1cs_open_wide_alloc(ctx, r, S); });
+}
+
+static int r1cs_open_system(k16_r1cs* r, const uint8_t* h_fixed, uint32_t max_wires, uint64_t* n_forced, uint64_t* n_free,
+                            uint64_t* n_undecided, uint64_t* n_skipped, uint64_t* n_absent, uint64_t* n_components, uint64_t* n_dims,
+                            uint32_t* h_wires, uint8_t* h_class, uint32_t cap, uint8_t* h_status, uint32_t* h_comp)
+{
     *n_forced = *n_free = *n_undecided = *n_skipped = *n_absent = *n_components = *n_dims = 0;
     k16_ctx* ctx = r->ctx;
     int      rc  = r1cs_open_begin(ctx, r, h_fixed);
     if (rc) return rc;
+    if ((rc = r1cs_open_wide_stage(ctx, r, max_wires))) return rc;
     ScanOpen& S = *r->scans->open;
-    r1cs_open_build(r->scans->pairs, S.index, r->n_wires, r->M, h_fixed, (const uint64_t*)S.h_verdict.p, &S.work);
+    r1cs_open_build(r->scans->pairs, S.index, r->n_wires, r->M, h_fixed, (const uint64_t*)S.h_verdict.p, &S.work, max_wires);
     if ((rc = r1cs_scan_drained(ctx, r1cs_open_run(ctx, r, false, 0)))) return rc;
     R1csOpenWork& Wk = S.work;
     uint64_t      dims = 0;
     for (size_t k = 0; k < Wk.comps.size(); k++) {
         const R1csOpenComp& c = Wk.comps[k];
         for (uint32_t j = 0; j < c.n_wires; j++) Wk.cls[Wk.wires[c.wire0 + j]] = S.h_cls[c.wire0 + j];
-        if (!c.n_cross) dims += c.n_wires - std::min<uint64_t>(S.h_out[3 * k], c.n_wires);
+        if (!c.n_cross) dims += c.n_wires - std::min<uint64_t>(r1cs_open_rank(r, k), c.n_wires);
     }
     uint64_t count[6] = {0, 0, 0, 0, 0, 0}, listed = 0;
     for (uint32_t i = 0; i < r->n_wires; i++) {
@@ -2223,15 +2528,36 @@ extern "C" int k16_r1cs_open_system(k16_r1cs* r, const uint8_t* h_fixed, uint64_
     *n_components = Wk.n_components;
     *n_dims       = dims;
     return K16_OK;
+}
+
+extern "C" int k16_r1cs_open_system(k16_r1cs* r, const uint8_t* h_fixed, uint64_t* n_forced, uint64_t* n_free, uint64_t* n_undecided,
+                                    uint64_t* n_skipped, uint64_t* n_absent, uint64_t* n_components, uint64_t* n_dims, uint32_t* h_wires,
+                                    uint8_t* h_class, uint32_t cap, uint8_t* h_status, uint32_t* h_comp)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !n_forced || !n_free || !n_undecided || !n_skipped || !n_absent || !n_components || !n_dims) return K16_ERR_ARG;
+    return r1cs_open_system(r, h_fixed, R1CS_OPEN_MAX_WIRES, n_forced, n_free, n_undecided, n_skipped, n_absent, n_components, n_dims, h_wires,
+                            h_class, cap, h_status, h_comp);
     });
 }
 
-extern "C" int k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint32_t wire, uint8_t* cls, uint32_t* comp_wires,
-                                       uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n, uint32_t* h_wires,
-                                       uint8_t* h_vals, uint32_t cap)
+extern "C" int k16_r1cs_open_system_ex(k16_r1cs* r, const uint8_t* h_fixed, uint32_t max_wires, uint64_t* n_forced, uint64_t* n_free,
+                                       uint64_t* n_undecided, uint64_t* n_skipped, uint64_t* n_absent, uint64_t* n_components,
+                                       uint64_t* n_dims, uint32_t* h_wires, uint8_t* h_class, uint32_t cap, uint8_t* h_status, uint32_t* h_comp)
 {
     return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
-    if (!r || !cls || !n) return K16_ERR_ARG;
+    if (!r || !n_forced || !n_free || !n_undecided || !n_skipped || !n_absent || !n_components || !n_dims) return K16_ERR_ARG;
+    const int rc = r1cs_open_cap(r->ctx, max_wires); // (before the counts are zeroed: a refused cap writes nothing)
+    if (rc) return rc;
+    return r1cs_open_system(r, h_fixed, max_wires, n_forced, n_free, n_undecided, n_skipped, n_absent, n_components, n_dims, h_wires, h_class,
+                            cap, h_status, h_comp);
+    });
+}
+
+static int r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint32_t max_wires, uint32_t wire, uint8_t* cls, uint32_t* comp_wires,
+                               uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n, uint32_t* h_wires, uint8_t* h_vals,
+                               uint32_t cap)
+{
     *cls = K16_OPEN_FIXED;
     *n   = 0;
     for (uint32_t* p : {comp_wires, comp_rows, comp_cross, rank})
@@ -2243,9 +2569,11 @@ extern "C" int k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint
     }
     int rc = r1cs_open_begin(ctx, r, h_fixed);
     if (rc) return rc;
+    if ((rc = r1cs_open_wide_stage(ctx, r, max_wires))) return rc;
     ScanOpen& S = *r->scans->open;
     uint32_t  nw = 0, nr = 0, nx = 0;
-    const uint8_t host = r1cs_open_one(r->scans->pairs, S.index, r->n_wires, r->M, h_fixed, (const uint64_t*)S.h_verdict.p, wire, &S.work, &nw, &nr, &nx);
+    const uint8_t host = r1cs_open_one(r->scans->pairs, S.index, r->n_wires, r->M, h_fixed, (const uint64_t*)S.h_verdict.p, wire, &S.work, &nw, &nr, &nx,
+                                       max_wires);
     if (comp_wires) *comp_wires = nw;
     if (comp_rows) *comp_rows = nr;
     if (comp_cross) *comp_cross = nx;
@@ -2256,11 +2584,14 @@ extern "C" int k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint
     *cls = K16_OPEN_FIXED;
     if ((rc = r1cs_scan_drained(ctx, r1cs_open_run(ctx, r, true, col)))) return rc;
     *cls = S.h_cls[col];
-    if (rank) *rank = (uint32_t)S.h_out[0];
+    if (rank) *rank = (uint32_t)r1cs_open_rank(r, 0);
     if (*cls != K16_OPEN_FREE) return K16_OK;
+    const bool     is_wide = nw > R1CS_OPEN_MAX_WIRES;
+    const Fr*      emit    = is_wide ? r->scans->open_wide->h_emit.p : S.h_emit.p;
+    const uint32_t width   = is_wide ? R1CS_OPEN_MAX_WIRES_EX : R1CS_OPEN_MAX_WIRES;
     uint64_t found = 0;
-    for (uint32_t j = 0; j < nw && j < 64; j++) {
-        const Fr& v = S.h_emit[j];
+    for (uint32_t j = 0; j < nw && j < width; j++) {
+        const Fr& v = emit[j];
         if (!(v.v[0] | v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7])) continue;
         if (found < cap) {
             if (h_wires) h_wires[found] = Wk.wires[j];
@@ -2270,6 +2601,27 @@ extern "C" int k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint
     }
     *n = found;
     return K16_OK;
+}
+
+extern "C" int k16_r1cs_open_direction(k16_r1cs* r, const uint8_t* h_fixed, uint32_t wire, uint8_t* cls, uint32_t* comp_wires,
+                                       uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n, uint32_t* h_wires,
+                                       uint8_t* h_vals, uint32_t cap)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !cls || !n) return K16_ERR_ARG;
+    return r1cs_open_direction(r, h_fixed, R1CS_OPEN_MAX_WIRES, wire, cls, comp_wires, comp_rows, comp_cross, rank, n, h_wires, h_vals, cap);
+    });
+}
+
+extern "C" int k16_r1cs_open_direction_ex(k16_r1cs* r, const uint8_t* h_fixed, uint32_t max_wires, uint32_t wire, uint8_t* cls,
+                                          uint32_t* comp_wires, uint32_t* comp_rows, uint32_t* comp_cross, uint32_t* rank, uint64_t* n,
+                                          uint32_t* h_wires, uint8_t* h_vals, uint32_t cap)
+{
+    return k16_guard(r ? r->ctx : nullptr, [&]() -> int {
+    if (!r || !cls || !n) return K16_ERR_ARG;
+    const int rc = r1cs_open_cap(r->ctx, max_wires); // (before *cls and *n are written: a refused cap writes nothing)
+    if (rc) return rc;
+    return r1cs_open_direction(r, h_fixed, max_wires, wire, cls, comp_wires, comp_rows, comp_cross, rank, n, h_wires, h_vals, cap);
     });
 }
 

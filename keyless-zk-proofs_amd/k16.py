@@ -51,6 +51,7 @@ SYMBOLS = [
     "k16_r1cs_unbound_wires", "k16_r1cs_wire_constraints", "k16_r1cs_incidences", "k16_r1cs_second_values",
     "k16_r1cs_determined_wires", "k16_r1cs_complete_witness", "k16_r1cs_complete_witness_ex", "k16_r1cs_boolean_wires",
     "k16_r1cs_determined_wires_ex", "k16_r1cs_held_wires", "k16_r1cs_open_system", "k16_r1cs_open_direction",
+    "k16_r1cs_open_system_ex", "k16_r1cs_open_direction_ex",
     "k16_prover_set_r1cs", "k16_prover_last_check", "k16_fullprover_set_r1cs", "k16_fullprover_last_rejection",
     "k16_r1cs_setup_size", "k16_r1cs_setup", "k16_r1cs_setup_file", "k16_generator_mul", "k16_generator_mul_info",
     "k16_msm_sharded_create", "k16_msm_sharded_destroy", "k16_msm_sharded_count", "k16_msm_sharded_range", "k16_msm_sharded_ctx",
@@ -193,6 +194,8 @@ def load():
     L.k16_r1cs_held_wires.argtypes = [vp, C.POINTER(u64), vp]
     L.k16_r1cs_open_system.argtypes = [vp, vp] + [C.POINTER(u64)] * 7 + [vp, vp, u32, vp, vp]
     L.k16_r1cs_open_direction.argtypes = [vp, vp, u32, C.POINTER(C.c_uint8)] + [C.POINTER(u32)] * 4 + [C.POINTER(u64), vp, vp, u32]
+    L.k16_r1cs_open_system_ex.argtypes = [vp, vp, u32] + [C.POINTER(u64)] * 7 + [vp, vp, u32, vp, vp]
+    L.k16_r1cs_open_direction_ex.argtypes = [vp, vp, u32, u32, C.POINTER(C.c_uint8)] + [C.POINTER(u32)] * 4 + [C.POINTER(u64), vp, vp, u32]
     L.k16_prover_set_r1cs.argtypes = [vp, vp]
     L.k16_prover_last_check.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), vp, u32]
     L.k16_fullprover_set_r1cs.argtypes = [vp, C.c_char_p]
@@ -552,7 +555,14 @@ SOLVE_RULE_LINEAR, SOLVE_RULE_BITS = 1, 2
 DET_RULE_PIN, DET_RULE_BITS = 1, 2
 OPEN_FIXED, OPEN_ABSENT, OPEN_FORCED, OPEN_FREE, OPEN_UNDECIDED, OPEN_SKIPPED = 0, 1, 2, 3, 4, 5
 OPEN_MAX_WIRES = 64                                                         # include/k16.h K16_OPEN_MAX_WIRES
+OPEN_MAX_WIRES_EX = 256                                                     # include/k16.h K16_OPEN_MAX_WIRES_EX
 OPEN_NO_COMPONENT = 0xFFFFFFFF
+
+
+def _max_wires(max_wires):
+    """the cap of an _ex call as the uint32 the library judges: what does not fit one is passed as a value it refuses"""
+    m = int(max_wires)
+    return m if 0 <= m <= 0xFFFFFFFF else 0
 
 
 def fullprover_set_r1cs(fullprover, r1cs_path):
@@ -852,13 +862,15 @@ class R1cs:
         mask[idx] = 1
         return mask
 
-    def open_system(self, fixed, cap=None, want_maps=False):
+    def open_system(self, fixed, cap=None, want_maps=False, max_wires=None):
         """k16_r1cs_open_system on the sums of the last completed check.  fixed: the wires held fixed -- a numpy array of
         dtype uint8 or bool with exactly n_wires elements is read as a mask (non-zero = fixed), anything else as a list of wires;
         wire 0 always is fixed.  Returns a dict: n_forced, n_free, n_undecided, n_skipped, n_absent,
         n_components, n_dims, and wires / classes -- the lowest min(cap, ...) wires that are neither OPEN_FIXED nor OPEN_ABSENT,
         ascending, with their OPEN_* class (cap=None asks for all).  want_maps=True adds status (the class of every wire,
-        uint8) and comp (the lowest wire of each wire's component, uint32, OPEN_NO_COMPONENT where there is none)."""
+        uint8) and comp (the lowest wire of each wire's component, uint32, OPEN_NO_COMPONENT where there is none).
+        max_wires=None is k16_r1cs_open_system itself; a number, OPEN_MAX_WIRES .. OPEN_MAX_WIRES_EX, goes to
+        k16_r1cs_open_system_ex: components of up to that many wires are eliminated, larger ones are OPEN_SKIPPED."""
         n_wires = self.info()["n_wires"]
         cap = n_wires if cap is None else int(cap)
         if cap < 0:
@@ -869,8 +881,11 @@ class R1cs:
         comp = np.zeros(n_wires, dtype=np.uint32) if want_maps else None
         names = ("n_forced", "n_free", "n_undecided", "n_skipped", "n_absent", "n_components", "n_dims")
         counts = [C.c_uint64() for _ in names]
-        self.ctx._chk(self.ctx.L.k16_r1cs_open_system(self.h, _p(mask), *(C.byref(c) for c in counts), _p(wires), _p(cls), cap,
-                                                      _p(status) if want_maps else None, _p(comp) if want_maps else None))
+        tail = [*(C.byref(c) for c in counts), _p(wires), _p(cls), cap, _p(status) if want_maps else None, _p(comp) if want_maps else None]
+        if max_wires is None:
+            self.ctx._chk(self.ctx.L.k16_r1cs_open_system(self.h, _p(mask), *tail))
+        else:
+            self.ctx._chk(self.ctx.L.k16_r1cs_open_system_ex(self.h, _p(mask), _max_wires(max_wires), *tail))
         out = {k: int(c.value) for k, c in zip(names, counts)}
         k = min(cap, out["n_forced"] + out["n_free"] + out["n_undecided"] + out["n_skipped"])
         out.update(wires=wires[:k].copy(), classes=cls[:k].copy())
@@ -878,33 +893,39 @@ class R1cs:
             out.update(status=status, comp=comp)
         return out
 
-    def open_direction(self, fixed, wire):
+    def open_direction(self, fixed, wire, max_wires=None):
         """k16_r1cs_open_direction: a dict with the wire's OPEN_* class (cls), its component's wires, LINEAR rows and CROSS
         constraints (comp_wires, comp_rows, comp_cross), the rank, and d: {wire: value} of the canonical direction -- empty
-        unless the wire is OPEN_FREE.  Adding d to the witness leaves every unbroken constraint satisfied."""
+        unless the wire is OPEN_FREE.  Adding d to the witness leaves every unbroken constraint satisfied.  max_wires=None is
+        k16_r1cs_open_direction itself; a number goes to k16_r1cs_open_direction_ex, with buffers of that many entries."""
         mask = self._fixed_mask(fixed)
         cls, n = C.c_uint8(), C.c_uint64()
         nums = [C.c_uint32() for _ in range(4)]
-        wires, vals = np.zeros(OPEN_MAX_WIRES, dtype=np.uint32), np.zeros((OPEN_MAX_WIRES, 32), dtype=np.uint8)
-        self.ctx._chk(self.ctx.L.k16_r1cs_open_direction(self.h, _p(mask), int(wire), C.byref(cls), *(C.byref(x) for x in nums),
-                                                         C.byref(n), _p(wires), _p(vals), OPEN_MAX_WIRES))
-        d = {int(wires[i]): int.from_bytes(vals[i].tobytes(), "little") for i in range(min(int(n.value), OPEN_MAX_WIRES))}
+        width = OPEN_MAX_WIRES if max_wires is None else max(1, min(_max_wires(max_wires), OPEN_MAX_WIRES_EX))
+        wires, vals = np.zeros(width, dtype=np.uint32), np.zeros((width, 32), dtype=np.uint8)
+        tail = [int(wire), C.byref(cls), *(C.byref(x) for x in nums), C.byref(n), _p(wires), _p(vals), width]
+        if max_wires is None:
+            self.ctx._chk(self.ctx.L.k16_r1cs_open_direction(self.h, _p(mask), *tail))
+        else:
+            self.ctx._chk(self.ctx.L.k16_r1cs_open_direction_ex(self.h, _p(mask), _max_wires(max_wires), *tail))
+        d = {int(wires[i]): int.from_bytes(vals[i].tobytes(), "little") for i in range(min(int(n.value), width))}
         return dict(cls=int(cls.value), comp_wires=nums[0].value, comp_rows=nums[1].value, comp_cross=nums[2].value,
                     rank=nums[3].value, d=d)
 
-    def audit(self, seed=None, rules=None, max_passes=64):
+    def audit(self, seed=None, rules=None, max_passes=64, max_wires=None):
         """The closure and the open-set solve in turns, until the solve forces nothing more: each pass runs the closure
         (determined_wires with `rules`) on the seed, holds fixed what is not DET_OPEN, runs open_system, and adds the FORCED wires
         to the seed -- they are forced given the fixed ones, so the next closure may start from them.  Returns (classes, forced_in,
         passes): the OPEN_* class of every wire after the last pass (a wire forced in an earlier pass is OPEN_FIXED there),
-        the pass (1, 2, ...) in which open_system forced each wire (0: never), and the number of passes."""
+        the pass (1, 2, ...) in which open_system forced each wire (0: never), and the number of passes.  max_wires: the cap
+        of open_system (None: k16_r1cs_open_system's own 64)."""
         n_wires = self.info()["n_wires"]
         forced_in = np.zeros(n_wires, dtype=np.uint32)
         for n_pass in range(1, int(max_passes) + 1):
             status = self.determined_wires(seed, cap=0, want_maps=True, rules=rules)[5]
             if seed is None:                                     # the closure's default seed: what this run called DET_SEED
                 seed = np.nonzero(status == DET_SEED)[0].tolist()
-            res = self.open_system(status != DET_OPEN, cap=0, want_maps=True)
+            res = self.open_system(status != DET_OPEN, cap=0, want_maps=True, max_wires=max_wires)
             forced = np.nonzero(res["status"] == OPEN_FORCED)[0]
             if forced.size == 0:
                 return res["status"], forced_in, n_pass

@@ -29,7 +29,7 @@ def main():
     if os.path.exists(out):
         os.unlink(out)
     blocks = re.split(r"remark: [^\n]*Function Name: ", p.stderr)[1:]
-    keys = [("VGPR", r"VGPRs"), ("AGPR", r"AGPRs"), ("scratch", r"ScratchSize \[bytes/lane\]"),
+    keys = [("SGPR", r"SGPRs"), ("VGPR", r"VGPRs"), ("AGPR", r"AGPRs"), ("scratch", r"ScratchSize \[bytes/lane\]"),
             ("occ", r"Occupancy \[waves/SIMD\]"), ("LDS", r"LDS Size \[bytes/block\]")]
     for b in blocks:
         name = b.split("\n")[0].split(" [-R")[0].strip()    # the compiler appends " [-Rpass-analysis=...]" to every remark
